@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- distinct states/sec of the BFS over raft.tla's Next on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set up, W warmup
+steps, K timed steps, one JSON line (``value``, ``ms_per_step``, the
+workload's counts under ``config``, and the roofline of the level kernel
+against the stored pure-stream ceiling).  ``--full`` adds the legs that take
+runs of their own: the live random-access calibration, the secondary
+wall-time-to-exhaust object of the default workload, and the CPU baseline
+(``--no-calib`` / ``--no-secondary`` / ``--no-cpu`` drop one of them again).
+``--dump-outputs DIR`` writes what the last timed step returned to its
+caller as ``DIR/<name>.npy`` (dump_outputs below).
 
 Workloads:
 
@@ -25,7 +35,7 @@ Workloads:
 * ``raft3_v2_t2_l2_m2`` and friends -- exhaustible analogues with a
   MaxInFlight bound (specs/MC.tla): a step is a complete model check (TLC's
   "0 states left on queue"), ms_per_step is the wall time to exhaust.  The
-  default run adds this as the secondary ``exhaust`` object.
+  default workload's ``--full`` run adds this as the secondary ``exhaust`` object.
 
 A "step" starts from the Init row on the device: no input crosses PCIe
 inside the timed region except ~200-byte counter read-backs per level.
@@ -496,6 +506,28 @@ def synthetic(run, args, rank, world, barrier):
     return max_over_ranks(timed, world) / args.steps, tot, n, per
 
 
+LEVEL_COLUMNS = ("level", "frontier", "new", "generated", "probes")
+
+
+def dump_outputs(path, levels=None, totals=None):
+    """--dump-outputs: what the last timed step handed its caller, as float64
+    arrays (every count is far below 2^53, so exact).  A BFS step returns the
+    per-level statistics: ``levels.npy`` holds one row per level with
+    LEVEL_COLUMNS -- the counts, not the times, so two builds of the library
+    can be compared output for output -- and ``totals.npy`` is (distinct,
+    generated, depth).  A synthetic step returns its sums: ``totals.npy`` is
+    (generated, probes, new).  There are no inputs to vary: a BFS starts from
+    the Init row, the synthetic inputs come from the fixed-seed generator."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if levels is not None:
+        np.save(os.path.join(path, "levels.npy"),
+                np.array([[getattr(lv, c) for c in LEVEL_COLUMNS] for lv in levels], dtype=np.float64))
+        totals = (sum(lv.new for lv in levels), sum(lv.generated for lv in levels),
+                  sum(1 for lv in levels if lv.new > 0))
+    np.save(os.path.join(path, "totals.npy"), np.array(totals, dtype=np.float64))
+
+
 def print_levels(name, levels):
     for lv in levels:
         print("%s level %3d frontier %12d new %12d generated %13d kernel %9.3f ms" %
@@ -508,6 +540,11 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=DEFAULT, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: live random-access calibration, the "
+                         "secondary wall-time-to-exhaust line of the default workload, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="distinct states in the CPU baseline sample (0 = per workload, ~10-30 s of CPU work)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use")
@@ -541,6 +578,10 @@ def main():
                     help="diagnostic: split the search on one GPU into this many fingerprint-owned shards "
                          "(the multi-GPU exchange protocol with device copies as transport)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: nothing that takes a run of its own beside the timed steps
+        args.no_cpu = args.no_secondary = args.no_calib = True
 
     rank, world, local = dist_env()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -578,6 +619,8 @@ def main():
     info = json.loads(run.ck.device_info())
     if args.workload == "synthetic":
         per_step, tot, n, per = synthetic(run, args, rank, world, barrier)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, totals=(tot["generated"], tot["probes"], tot["new"]))
         pool = args.synth_pool
         S = run.ck.levels[0].row_bytes if run.ck.levels else 4 * rtla.row_words(run.cfg)
         ems = tot["kernel_ms"]
@@ -636,6 +679,8 @@ def main():
             dist.destroy_process_group()
         return
     per_step, levels = timed(run, args.steps, args.warmup, world, barrier, args.cap_levels)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, levels=levels)
     distinct = sum(lv.new for lv in levels)
     generated = sum(lv.generated for lv in levels)
     depth = sum(1 for lv in levels if lv.new > 0)

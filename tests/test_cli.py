@@ -26,9 +26,17 @@ def test_reference_cfg_names_an_undefined_invariant():
             "specification.") in r.stdout
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference not mounted")
 def test_modified_spec_is_refused(tmp_path):
-    """The semantics are compiled in: any raft.tla but the reference's is refused."""
+    """The semantics are compiled in: any raft.tla but the reference's is
+    refused -- a module of that name that is not the spec (needs nothing
+    outside the repository) and, where the reference is mounted, its own text
+    with one comment line appended."""
+    open(tmp_path / "raft.tla", "w").write("---- MODULE raft ----\nEXTENDS Naturals\nVARIABLE x\n====\n")
+    open(tmp_path / "raft.cfg", "w").write("SPECIFICATION Spec\nINVARIANT NoTwoLeaders\n")
+    r = run(["-config", str(tmp_path / "raft.cfg"), str(tmp_path / "raft.tla")])
+    assert r.returncode == 150 and "has sha256" in r.stdout and "verified" not in r.stdout, r.stdout
+    if not HAVE_REF:
+        return
     text = open(os.path.join(REF, "raft.tla")).read()
     open(tmp_path / "raft.tla", "w").write(text + "\n\\* edited\n")
     shutil.copy(os.path.join(REF, "raft.cfg"), tmp_path / "raft.cfg")

@@ -72,6 +72,25 @@ def test_fpset_per_rank_sizing():
     assert bench.fpset_log2_for("cfg2", 8, pinned=False) == bench.fpset_log2_for("cfg2", 1)
 
 
+def test_dump_outputs_holds_the_counts_not_the_times(tmp_path):
+    """--dump-outputs: float64 arrays of a step's level counts (the times
+    differ from run to run and stay out), exact at the sizes the bench reaches."""
+    import types
+
+    import numpy as np
+    big = 5_275_111_690  # > 2^32: the default workload's generated total
+    levels = [types.SimpleNamespace(level=1, frontier=0, new=1, generated=1, probes=0, seconds=0.25, expand_ms=0.0),
+              types.SimpleNamespace(level=2, frontier=1, new=3, generated=big, probes=7, seconds=0.5, expand_ms=1.5),
+              types.SimpleNamespace(level=3, frontier=3, new=0, generated=4, probes=2, seconds=0.75, expand_ms=2.5)]
+    bench.dump_outputs(str(tmp_path / "a" / "b"), levels=levels)
+    lv = np.load(tmp_path / "a" / "b" / "levels.npy")
+    assert lv.dtype == np.float64 and lv.tolist() == [[1, 0, 1, 1, 0], [2, 1, 3, big, 7], [3, 3, 0, 4, 2]]
+    assert np.load(tmp_path / "a" / "b" / "totals.npy").tolist() == [4, big + 5, 2]
+    bench.dump_outputs(str(tmp_path / "s"), totals=(10, 8, 5))  # the synthetic workload's sums
+    assert sorted(os.listdir(tmp_path / "s")) == ["totals.npy"]
+    assert np.load(tmp_path / "s" / "totals.npy").tolist() == [10, 8, 5]
+
+
 def test_bench_gpus_flag_launches_ranks():
     """`bench.py --gpus 2` with no launcher starts 2 ranks under
     torch.distributed.run as a child process; both reach the process group

@@ -1122,3 +1122,35 @@ def test_bench_gpus_over_shm_matches_golden(gpus):
     c = r["config"]
     assert r["n_gpus"] == gpus and c["parallelism"] == "fp-sharded%d" % gpus and c["exhausted"]
     assert (c["distinct"], c["generated"], c["depth"]) == (g["distinct"], g["generated"], g["depth"])
+
+
+def test_bench_plain_run_dumps_the_last_steps_levels(tmp_path):
+    """A plain `bench.py` run (no --full) times its steps and nothing else --
+    no CPU baseline, no secondary line, no live calibration -- and
+    --dump-outputs writes the level counts the last timed step returned:
+    levels.npy (level, frontier, new, generated, probes) and totals.npy
+    (distinct, generated, depth), here the golden counts of an exhausted model."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    g = GOLD["n3_v1_t2_l1_m1"]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload",
+                        "raft3_v1_t2_l1_m1", "--mem-budget", "8", "--fpset-log2", "24", "--steps", "2",
+                        "--warmup", "0", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["config"]["exhausted"]
+    assert r["value"] == pytest.approx(g["distinct"] / (r["ms_per_step"] / 1e3))
+    assert r["cpu_baseline"] is None and "exhaust" not in r and r["roofline"]["random_access"]["calibration"] is None
+    assert sorted(os.listdir(tmp_path / "out")) == ["levels.npy", "totals.npy"]
+    lv = np.load(tmp_path / "out" / "levels.npy")
+    assert lv.dtype == np.float64 and lv.shape == (len(g["levels"]), 5)
+    assert lv[:, 0].tolist() == list(range(1, len(g["levels"]) + 1))
+    assert lv[:, 2:4].tolist() == g["levels"]
+    assert lv[1:, 1].tolist() == lv[:-1, 2].tolist()  # a level's frontier is the level before it
+    assert np.load(tmp_path / "out" / "totals.npy").tolist() == [g["distinct"], g["generated"], g["depth"]]

@@ -7,7 +7,7 @@ O=gpurun_out/cmp; mkdir -p $O
 while IFS='|' read -r name envs args; do
   [ -z "$name" ] && continue
   echo "== $name $(date +%T)"
-  env $envs timeout -k 10 ${LIMIT:-300} python -u bench.py --no-cpu --no-secondary $args > $O/$name.json 2> $O/$name.err \
+  env $envs timeout -k 10 ${LIMIT:-300} python -u bench.py --full --no-cpu --no-secondary $args > $O/$name.json 2> $O/$name.err \
     || { tail -5 $O/$name.err; exit 1; }
   python -c "
 import json; r=json.loads([l for l in open('$O/$name.json') if l.startswith('{')][-1]); f=r['roofline']; c=r['config']

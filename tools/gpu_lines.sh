@@ -8,7 +8,7 @@ O=gpurun_out/lines; mkdir -p $O
 IFS=';' read -ra ENTRIES <<< "${LINES:-cfg2|--workload cfg2}"
 for ent in "${ENTRIES[@]}"; do
   tag=${ent%%|*}; args=${ent#*|}
-  timeout -k 10 ${LIMIT:-400} python -u bench.py --no-cpu --no-secondary $args > $O/$tag.json 2> $O/$tag.err \
+  timeout -k 10 ${LIMIT:-400} python -u bench.py --full --no-cpu --no-secondary $args > $O/$tag.json 2> $O/$tag.err \
     || { echo "FAILED $tag"; tail -20 $O/$tag.err; exit 1; }
   python -c "
 import json; r=json.load(open('$O/$tag.json')); f=r['roofline']; ra=f['random_access']
