@@ -282,6 +282,24 @@ int expand_blocks_per_cu(const Layout& L) {
   return b < 1 ? 1 : (b > 8 ? 8 : b);
 }
 
+// The instantiation of k_expand_compact for a's layout: the compiled-in
+// BASELINE layouts first, then the run-time layout.  *done = one took it.
+static hipError_t launch_compact_any(const CompactArgs& a, bool* done) {
+  hipError_t e = hipSuccess;
+  *done = false;
+  if (!(a.xflags & XF_NO_SPECIAL)) {
+    e = launch_compact_spec_a(a, done);
+    if (!*done) e = launch_compact_spec_b(a, done);
+  }
+#ifndef RTLA_EXP_MINIMAL  // perf experiments: compiled-in layouts only (fast builds)
+  if (!*done && a.L.sym) e = launch_compact_sym_a(a, done);
+  if (!*done && a.L.sym) e = launch_compact_sym_b(a, done);
+  if (!*done) e = launch_compact_generic_a(a, done);
+  if (!*done) e = launch_compact_generic_b(a, done);
+#endif
+  return e;
+}
+
 hipError_t launch_expand(const Layout& L, const Ring& cur, uint64_t s_begin, uint64_t s_end, uint64_t cur_base,
                          const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap, uint64_t* table,
                          int tlog2, DevCounters* ctr, const ShardBox& box, int grid, hipStream_t st, int xflags,
@@ -292,19 +310,8 @@ hipError_t launch_expand(const Layout& L, const Ring& cur, uint64_t s_begin, uin
     const CompactArgs a{L,         box.nshard > 1, cur,      s_begin, s_end,  cur_base, next,   parents, next_base,
                         next_cap,  table,          tlog2,    ctr,     box,    st,       xflags, sent,
                         (xflags & XF_BLOCK4) ? cwpb : 1};  // one-wave workgroups by default
-    hipError_t e = hipSuccess;
     bool done = false;
-    // the compiled-in BASELINE layouts first, then the run-time layout
-    if (!(xflags & XF_NO_SPECIAL)) {
-      e = launch_compact_spec_a(a, &done);
-      if (!done) e = launch_compact_spec_b(a, &done);
-    }
-#ifndef RTLA_EXP_MINIMAL  // perf experiments: compiled-in layouts only (fast builds)
-    if (!done && L.sym) e = launch_compact_sym_a(a, &done);
-    if (!done && L.sym) e = launch_compact_sym_b(a, &done);
-    if (!done) e = launch_compact_generic_a(a, &done);
-    if (!done) e = launch_compact_generic_b(a, &done);
-#endif
+    hipError_t e = launch_compact_any(a, &done);
     if (!done) return hipErrorNotSupported;
     if (e != hipSuccess) return e;
     if (mid) {
@@ -334,16 +341,7 @@ bool level_kernel_shape(const Layout& L, bool multi, int xflags, int* waves, int
   a.box.nshard = multi ? 2 : 1;
   a.query = q;
   bool done = false;
-  if (!(xflags & XF_NO_SPECIAL)) {
-    (void)launch_compact_spec_a(a, &done);
-    if (!done) (void)launch_compact_spec_b(a, &done);
-  }
-#ifndef RTLA_EXP_MINIMAL
-  if (!done && L.sym) (void)launch_compact_sym_a(a, &done);
-  if (!done && L.sym) (void)launch_compact_sym_b(a, &done);
-  if (!done) (void)launch_compact_generic_a(a, &done);
-  if (!done) (void)launch_compact_generic_b(a, &done);
-#endif
+  (void)launch_compact_any(a, &done);
   if (!done || q[0] <= 0 || q[1] <= 0) return false;
   *waves = q[0];
   *group = q[1];

@@ -12,7 +12,6 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "rtla_device.h"
 
@@ -37,23 +36,9 @@ __device__ __forceinline__ unsigned long long shfl0_u64(unsigned long long v) {
   return (unsigned long long)lo | (unsigned long long)hi << 32;
 }
 
-// Copy n contiguous words global -> LDS with 8 loads in flight per lane
-// (a plain loop waits for every load before its LDS store).
-__device__ __forceinline__ void copy_words_lds(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int n,
-                                               int lane) {
-  int w = lane;
-  for (; w + 7 * 64 < n; w += 8 * 64) {
-    uint32_t v[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = src[w + j * 64];
-#pragma unroll
-    for (int j = 0; j < 8; j++) dst[w + j * 64] = v[j];
-  }
-  for (; w < n; w += 64) dst[w] = src[w];
-}
-
-// The same with 16-byte accesses (dst and src 16-byte aligned): a quarter of
-// the load instructions and 4x the bytes in flight per lane.
+// Copy n contiguous words global -> LDS (dst and src 16-byte aligned) with 8
+// 16-byte loads in flight per lane (a plain loop waits for every load before
+// its LDS store).
 __device__ __forceinline__ void copy_words_lds16(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int n,
                                                  int lane) {
   const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
@@ -206,9 +191,7 @@ __device__ __forceinline__ int inst_family(const Layout& L, int inst) {
 }
 
 __device__ __forceinline__ int cover_code(const Layout& L, int inst, int sub) {
-  int fam = 0;
-#pragma unroll
-  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
+  const int fam = inst_family(L, inst);
   return fam == F_RECEIVE ? F_COUNT + sub : fam;
 }
 
@@ -264,25 +247,6 @@ __device__ __forceinline__ FP successor_orbit_key(const Layout& L, P prow, const
   });
 }
 
-// The orbit key in steps of one image (key_chunk's continuations): images
-// [k, k + 1) of the successor parent + d -- or [k, |C(s)|) when `all` --
-// folded into best (the least image fingerprint so far).  Returns the next
-// image's index, or -1 once best is the least image (the key is then
-// orbit_key_finish(best) + fp(allLogs'), as sym_key's).
-template <int NS, class P>
-__device__ __forceinline__ int successor_orbit_step(const Layout& L, P prow, const DeltaT<NS>& d, int k, bool all,
-                                                    FP& best) {
-  return with_successor<NS>(L, prow, d, [&](auto rec_of, int nmsg, auto slot_of, int nelec, auto elec_of) {
-    const SymRank r = sym_rank<NS>(L, rec_of, nmsg, slot_of, nelec, elec_of);
-    const int k1 = all ? r.ncomb : min(k + 1, r.ncomb);
-    for (int j = k; j < k1; j++) {
-      const FP f = sym_image_fp<NS>(L, rec_of, nmsg, slot_of, nelec, elec_of, r, j);
-      if (fp_less(f, best)) best = f;
-    }
-    return k1 < r.ncomb ? k1 : -1;
-  });
-}
-
 // a[j] += v for a run-time j (selects)
 template <int NS>
 __device__ __forceinline__ void add_at(uint32_t* a, uint32_t j, uint32_t v) {
@@ -290,12 +254,17 @@ __device__ __forceinline__ void add_at(uint32_t* a, uint32_t j, uint32_t v) {
   for (int k = 0; k < NS; k++)
     if ((uint32_t)k == j) a[k] += v;
 }
-// successor_orbit_step with the successor's signatures PATCHED from the
-// parent's parts (psg[w * S], w < 3 * NS: srv_sig, sent and received message
-// sums per server, computed once per parent row): the changed server's local
-// part is recomputed, each bag write moves its old slot's share out of and
-// its new slot's share into the sums -- no pass over the successor's bag and
-// records.  The same signatures, hence the same key, as sym_rank's.
+// The orbit key in steps of one image (key_chunk's continuations): images
+// [k, k + 1) of the successor parent + d -- or [k, |C(s)|) when `all` --
+// folded into best (the least image fingerprint so far).  Returns the next
+// image's index, or -1 once best is the least image (the key is then
+// orbit_key_finish(best) + fp(allLogs'), as sym_key's).
+// The successor's signatures are PATCHED from the parent's parts (psg[w * S],
+// w < 3 * NS: srv_sig, sent and received message sums per server, computed
+// once per parent row): the changed server's local part is recomputed, each
+// bag write moves its old slot's share out of and its new slot's share into
+// the sums -- no pass over the successor's bag and records.  The same
+// signatures, hence the same key, as sym_rank's.
 template <int NS, int S, class P>
 __device__ __forceinline__ int successor_orbit_step_sig(const Layout& L, P prow, const DeltaT<NS>& d,
                                                         const uint32_t* psg, int k, bool all, FP& best) {
@@ -500,31 +469,6 @@ __device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int
 #define RTLA_SYM_WAVES_PER_EU 4      // SYMMETRY, the key pass a call of its own (key_one): 128 VGPRs (configs[3]:
                                      // 311.5 ms, 16-state groups) beat 168 (343 ms) and 102 (414 ms)
 #endif
-#ifndef RTLA_DUP_COUNTED
-#define RTLA_DUP_COUNTED 1  // 0: evaluate every DuplicateMessage successor (A/B builds)
-#endif
-#ifndef RTLA_DUP_NARROW
-#define RTLA_DUP_NARROW 0   // 1: count them in the narrow-row kernels too (A/B builds)
-#endif
-#ifndef RTLA_MULTI_ASYNC
-#define RTLA_MULTI_ASYNC 1  // multi-shard kernels pipeline their CAS too
-#endif
-#ifndef RTLA_RECV_GROUP
-#define RTLA_RECV_GROUP 2  // Receive pairs grouped by message type in the pair ring (4 ballots per
-                           // instance): 2 = only for SYMMETRY and max copies > 1 (round 6 A/B,
-                           // profiles/r06_v2/recvgrp_*: ungrouped configs[1] 178.1 vs 179.7 ms,
-                           // configs[0] 257.0 vs 263.3, the exhaust model 1148 vs 1211; grouped
-                           // configs[2] 89.4 vs 91.2, configs[3] 288.7 vs 293.6); 0 / 1 never / always
-#endif
-#ifndef RTLA_SPECIALISE
-#define RTLA_SPECIALISE 1  // 0: no per-family copies of compute_delta in the evaluation pass (A/B)
-#endif
-#ifndef RTLA_FAMILY_CUT
-#define RTLA_FAMILY_CUT 0  // > 0: a chunk is cut at a family boundary once this many pairs are queued
-#endif                     // (0: per kernel, family_cut below)
-#ifndef RTLA_SYM_SPLIT
-#define RTLA_SYM_SPLIT 1  // SYMMETRY: orbit keys in a pass of their own (key_chunk), not inside the evaluation
-#endif
 // The layout the kernel runs on: the run-time argument, or (LC.N != 0) the
 // configuration compiled in as a template parameter, whose fields the
 // compiler then folds into every offset, bound and loop of the model code.
@@ -536,7 +480,7 @@ __device__ __forceinline__ const Layout& pick_layout(const Layout& rt) {
 
 namespace {
 // One key_chunk lane as a function of its own: the successor's Delta, then
-// successor_orbit_step from image k with the least image so far best0.
+// successor_orbit_step_sig from image k with the least image so far best0.
 // next >= 0: f is the least image so far and image `next` is due; next ==
 // -1: f is the orbit key; next == -2: the instance is not enabled.  NOT
 // inlined, so that its registers are allocated apart from the level
@@ -570,9 +514,6 @@ __device__ __noinline__ KeyStep key_one(const Layout& Lrt, const uint32_t* prow,
 // row differs from the parent's copy (child_write; `wait`: the copies must
 // land first).  NOT inlined for the same reason as key_one: at the SYMMETRY
 // kernel's 128 VGPRs the inlined build pass is one of the two big spillers.
-#ifndef RTLA_SYM_BUILD_CALL
-#define RTLA_SYM_BUILD_CALL 1
-#endif
 struct BuildOut {
   int bad, sub, in_model;
 };
@@ -626,9 +567,8 @@ __device__ __noinline__ BuildOut build_one(const Layout& Lrt, const uint32_t* pr
 // GROUP: frontier states per wave-group (64, or 32 for wide rows: halves the
 // LDS tile so more waves fit a CU).  LC: compiled-in layout (Layout{} = use
 // the run-time argument Lrt).  SYM: SYMMETRY Permutations(Server) -- the
-// probe pass evaluates the full Delta of each successor and probes its orbit
-// key (successor_orbit_key) instead of its fingerprint; rows keep the states
-// themselves.
+// successors are probed by their orbit key, computed in a pass of its own
+// (key_chunk), instead of their fingerprint; rows keep the states themselves.
 // Waves per SIMD the level kernel's registers are budgeted for: narrow
 // compiled-in rows (<= 32 words: the exhaust model's 84 B) fit 4 (128
 // VGPRs; its 74 levels 1259 -> 1158 ms; 5 waves: 1605 ms), wider ones 3 (at 4: configs[1]
@@ -652,7 +592,6 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
                  unsigned long long next_base, unsigned long long next_cap, unsigned long long* table,
                  unsigned long long* sent, int tlog2, DevCounters* ctr, ShardBox box, int xflags) {
   const Layout& L = pick_layout<LC>(Lrt);
-  constexpr bool KSPLIT = SYM && RTLA_SYM_SPLIT;
   const int me = box.me;
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ unsigned int cov[2 * COVER_CODES];
@@ -703,16 +642,25 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   // (not in the narrow-row kernels at 4 waves/SIMD: the exhaust model's spills
   // grow 39 -> 58 VGPRs with it and its run slows 1156 -> 1320 ms)
   constexpr bool narrow = !SYM && LC.N != 0 && LC.W <= RTLA_NARROW_W;
-  const bool dup_counted = RTLA_DUP_COUNTED && (!narrow || RTLA_DUP_NARROW) && L.C == 1 &&
-                           !(xflags & (XF_ALL_SUCCESSORS | XF_NO_CHUNKS));
-  const bool recv_group = RTLA_RECV_GROUP == 1 || (RTLA_RECV_GROUP == 2 && (SYM || L.C > 1));
+  // (after the round-6 pair-ring changes, counting them there too measured
+  // 1122.3 vs 1145 ms on the exhaust model, profiles/r06_v6/fpset_ab.txt:
+  // found late and not adopted yet -- turning this on is a performance change)
+  constexpr bool dup_narrow = false;
+  const bool dup_counted = (!narrow || dup_narrow) && L.C == 1 && !(xflags & (XF_ALL_SUCCESSORS | XF_NO_CHUNKS));
+  // Receive pairs are grouped by message type in the pair ring (4 ballots per
+  // instance) only for SYMMETRY and max copies > 1 (round 6,
+  // profiles/r06_v2/pairring_ab.txt: ungrouped configs[1] 178.1 vs 179.7 ms,
+  // configs[0] 257.0 vs 263.3, the exhaust model 1148 vs 1211; grouped
+  // configs[2] 89.4 vs 91.2, configs[3] 288.7 vs 293.6)
+  const bool recv_group = SYM || L.C > 1;
   // A chunk is cut at a family boundary once family_cut pairs are queued, so
   // that it holds one family and runs compute_delta specialised for it;
-  // 64 = never: full chunks of mixed families (round 6 sweep, profiles/r06_v2/
-  // cut*: 22 -> 64 takes configs[1] 178.3 -> 170.0 ms, configs[0] 258.6 ->
-  // 245.6, configs[2] 90.4 -> 87.3; the SYMMETRY kernel is best at 40 (285.9
-  // vs 287.1 / 291.6), the narrow-row exhaust kernel at 22 (1145 vs 1153))
-  constexpr int family_cut = RTLA_FAMILY_CUT ? RTLA_FAMILY_CUT : narrow ? 22 : SYM ? 40 : 64;
+  // 64 = never: full chunks of mixed families (round 6 sweep,
+  // profiles/r06_v2/pairring_ab.txt: 22 -> 64 takes configs[1] 178.3 -> 170.0
+  // ms, configs[0] 258.6 -> 245.6, configs[2] 90.4 -> 87.3; the SYMMETRY
+  // kernel is best at 40 (285.9 vs 287.1 / 291.6), the narrow-row exhaust
+  // kernel at 22 (1145 vs 1153))
+  constexpr int family_cut = narrow ? 22 : SYM ? 40 : 64;
   RTLA_STAMP_DECL
   // pending probe (issued by the previous chunk).  MULTI: a successor owned
   // by another shard probes this shard's SENT cache instead of the set --
@@ -733,7 +681,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   // and that CAS is resolved a chunk later: neither the insert nor the first
   // collision step waits for a round trip.  (MULTI, a successor another
   // shard owns: the sent-cache store instead, see above.)
-  const bool async_cas = (!MULTI || RTLA_MULTI_ASYNC) && !(xflags & XF_CAS_ONLY);
+  const bool async_cas = !(xflags & XF_CAS_ONLY);
   bool cpend = false;    // CAS set up by resolve(), issued by issue_cas()
   bool cflight = false;  // CAS in flight (result in cold)
   unsigned long long cold = 0, ckey = 0, cidx = 0;
@@ -747,28 +695,13 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   unsigned long long dedup_new = 0;  // XF_DEDUP_ONLY: new fingerprints (uniform)
   unsigned long long s0 = 0;  // first state of the current group
 
-  // Build the rows of every pending new state (probes drained), one
-  // next-level slot reservation for all of them (slots past next_cap are
-  // dropped and flagged: the level is then reported incomplete):
-  //  (1) the wave copies each parent row (LDS) to its child's slot with
-  //      coalesced stores, for all of them (copying per batch of 64 instead,
-  //      so that the patches reach lines still in L2, was measured: no
-  //      fewer HBM writes, 5 % slower);
-  //  (2) per batch of 64, one state per lane: its full Delta (compute_delta
-  //      with slot bookkeeping; the probe pass only folded it into a hash),
-  //      fingerprint, invariants and distinct coverage -- the first batch's
-  //      arithmetic overlaps the copies in flight;
-  //  (3) after the copies landed (one wait), each lane stores the words in
-  //      which its child differs from the parent (child_write, rtla_model.h).
-  // No separate row-building kernel: no parent-record read, no parent-row
-  // gather, no second launch.
   // compute_delta over a chunk of lanes, specialised for its family when the
   // whole chunk holds one (D = DeltaFpT for the probe pass, DeltaT for the
   // row build and orbit keys)
   auto chunk_delta = [&](bool active, const uint32_t* prow, int inst, auto& d) {
     const int f0 = inst_family(L, __builtin_amdgcn_readfirstlane(inst));
     const bool one_family = __ballot(active && inst_family(L, inst) != f0) == 0ull;
-    if (!RTLA_SPECIALISE || !one_family || (xflags & XF_GENERIC_DELTA)) {
+    if (!one_family || (xflags & XF_GENERIC_DELTA)) {
       if (active) compute_delta<NS>(L, prow, inst, d);
     } else if (active) {
       switch (f0) {  // one family in the whole chunk: its code only
@@ -785,6 +718,36 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       }
     }
   };
+  // Coverage tally of one pass (base = cov: generated, cov + COVER_CODES:
+  // distinct), aggregated over equal codes: the lanes that share the first
+  // counting lane's code cost one atomic together.
+  auto cover_add = [&](unsigned* base, bool on, int inst, int sub) {
+    if (xflags & XF_NO_COVER) return;
+    const int code = on ? cover_code(L, inst, sub) : -1;
+    const unsigned long long m = __ballot(on);
+    if (m) {
+      const int c0 = __shfl(code, __builtin_ctzll(m));
+      const bool same = on && code == c0;
+      const int n0 = __popcll(__ballot(same));
+      if (lane == 0) atomicAdd(&base[c0], (unsigned)n0);
+      if (on && !same) atomicAdd(&base[code], 1u);
+    }
+  };
+  // Build the rows of every pending new state (probes drained), one
+  // next-level slot reservation for all of them (slots past next_cap are
+  // dropped and flagged: the level is then reported incomplete):
+  //  (1) the wave copies each parent row (LDS) to its child's slot with
+  //      coalesced stores, for all of them (copying per batch of 64 instead,
+  //      so that the patches reach lines still in L2, was measured: no
+  //      fewer HBM writes, 5 % slower);
+  //  (2) per batch of 64, one state per lane: its full Delta (compute_delta
+  //      with slot bookkeeping; the probe pass only folded it into a hash),
+  //      fingerprint, invariants and distinct coverage -- the first batch's
+  //      arithmetic overlaps the copies in flight;
+  //  (3) after the copies landed (one wait), each lane stores the words in
+  //      which its child differs from the parent (child_write, rtla_model.h).
+  // No separate row-building kernel: no parent-record read, no parent-row
+  // gather, no second launch.
   auto build_all = [&]() {
     const int ntot = tail - head;  // uniform
     if (ntot == 0) return;
@@ -820,7 +783,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       const int e = act ? newl[(head + b + lane) & (NEWCAP - 1)] : 0;
       const int sl = e >> 8, inst = e & 255;
       const int child = b + lane;  // index in the run
-      if constexpr (SYM && RTLA_SYM_BUILD_CALL) {  // the lane's work as a call of its own (build_one)
+      if constexpr (SYM) {  // the lane's work as a call of its own (build_one)
         BuildOut o{0, 0, 0};
         if (act)
           o = build_one<NS, LC, GROUP>(Lrt, rows + sl * W, inst, pfpl[sl], pall + sl, d1, next.base, n1, child * W,
@@ -833,17 +796,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
           ctr->viol_in_model = 1;
           ctr->viol_child = child < nrows ? next_base + obase + child : ~0ull;
         }
-        if (!(xflags & XF_NO_COVER)) {
-          const int code = act ? cover_code(L, inst, o.sub) : -1;
-          const unsigned long long am = __ballot(act);
-          if (am) {
-            const int c0 = __shfl(code, __builtin_ctzll(am));
-            const bool same = act && code == c0;
-            const int n0 = __popcll(__ballot(same));
-            if (lane == 0) atomicAdd(&cov[COVER_CODES + c0], (unsigned)n0);
-            if (act && !same) atomicAdd(&cov[COVER_CODES + code], 1u);
-          }
-        }
+        cover_add(cov + COVER_CODES, act, inst, o.sub);  // distinct coverage
         if (child < nrows && RTLA_IDX_OK(ctr, next_base + obase + child, ctr->cap_parents))
           parents[next_base + obase + child] =
               (xflags & XF_ALL_SUCCESSORS)
@@ -869,17 +822,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
         ctr->viol_in_model = 1;
         ctr->viol_child = child < nrows ? next_base + obase + child : ~0ull;
       }
-      if (!(xflags & XF_NO_COVER)) {  // distinct coverage, aggregated over equal codes
-        const int code = act ? cover_code(L, inst, d.sub) : -1;
-        const unsigned long long am = __ballot(act);
-        if (am) {
-          const int c0 = __shfl(code, __builtin_ctzll(am));
-          const bool same = act && code == c0;
-          const int n0 = __popcll(__ballot(same));
-          if (lane == 0) atomicAdd(&cov[COVER_CODES + c0], (unsigned)n0);
-          if (act && !same) atomicAdd(&cov[COVER_CODES + code], 1u);
-        }
-      }
+      cover_add(cov + COVER_CODES, act, inst, d.sub);  // distinct coverage
       uint32_t spk[PACKW], epk[PACKW];  // the changed records, packed
       if (act) child_pack(L, d, spk, epk);
       if (rows_on) {  // (3): the copies must land first (same words, other lanes)
@@ -1042,7 +985,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     const int sl = e >> 8, inst = e & 255;
     const uint32_t* prow = rows + sl * W;
     const FP qfp = pfpl[sl];
-    std::conditional_t<SYM && !KSPLIT, DeltaT<NS>, DeltaFpT<NS>> d;
+    DeltaFpT<NS> d;
     d.enabled = 0;
     if (!(xflags & XF_NO_DELTA)) chunk_delta(active, prow, inst, d);
     bool en = d.enabled != 0;
@@ -1060,19 +1003,14 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     if (en && (xflags & XF_ALL_SUCCESSORS)) {
       nprobe = true;  // "probe" = output it: issue_probe skips the load, resolve takes it as new
     } else if (en && d.in_model) {
-      FP cfp;
-      if constexpr (SYM && !KSPLIT) cfp = fp_add(qfp, delta_fp<NS>(L, prow, d));
-      else
-        cfp = (xflags & XF_NO_HASH) ? FP{qfp.a + d.rec[0] + (uint64_t)d.fmsg.a, qfp.b + d.rec[1]}
-                                    : fp_add(qfp, delta_fp<NS>(L, prow, d));
+      const FP cfp = (xflags & XF_NO_HASH) ? FP{qfp.a + d.rec[0] + (uint64_t)d.fmsg.a, qfp.b + d.rec[1]}
+                                           : fp_add(qfp, delta_fp<NS>(L, prow, d));
       const FP qfp0 = row_fp(prow);
       if (cfp.a != qfp0.a || cfp.b != qfp0.b) {  // successor == parent: already in the set
-        if constexpr (KSPLIT) {
+        if constexpr (SYM) {
           kq = true;  // its seen-set key is the orbit key: queued for key_chunk
         } else {
-          // seen-set key: the fingerprint, or (SYMMETRY, not split) the orbit key
-          FP key = cfp;
-          if constexpr (SYM) key = successor_orbit_key<NS>(L, prow, d, afpl[sl]);
+          const FP key = cfp;  // seen-set key: the fingerprint
           nprobe = !(xflags & XF_NO_PROBE);
           ncf = key;
           nowner = MULTI ? fp_owner(key, box.nshard) : me;
@@ -1080,22 +1018,12 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
         }
       }
     }
-    if constexpr (KSPLIT) {
+    if constexpr (SYM) {
       const unsigned long long km = __ballot(kq);
       if (kq) kring[(kpos + __popcll(km & lanes_below)) & (RING - 1)] = (uint16_t)(sl << 8 | inst);
       kpos += __popcll(km);
     }
-    if (!(xflags & XF_NO_COVER)) {  // generated coverage, aggregated over equal codes
-      const int code = en ? cover_code(L, inst, d.sub) : -1;
-      const unsigned long long em = __ballot(en);
-      if (em) {
-        const int c0 = __shfl(code, __builtin_ctzll(em));
-        const bool same = en && code == c0;
-        const int n0 = __popcll(__ballot(same));
-        if (lane == 0) atomicAdd(&cov[c0], (unsigned)n0);
-        if (en && !same) atomicAdd(&cov[code], 1u);
-      }
-    }
+    cover_add(cov, en, inst, d.sub);  // generated coverage
     // out-of-model successors: checked, never stored (not in the
     // synthetic microbench, whose random states are no model's)
     int bad = 0;
@@ -1256,7 +1184,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       pfpl[lane] = fp_add(row_fp(prow_mine), alllogs_delta<NS>(L, prow_mine, pall_mine));
       if (SYM) afpl[lane] = alllogs_fp(L, pall_mine);
       nmsg = row_nmsg(L, prow_mine);
-      if constexpr (KSPLIT) {
+      if constexpr (SYM) {
         uint32_t loc[NS], ms[NS], mr[NS];
         sym_sig_parts<NS>(L, [&](int i, uint32_t* out) { load_rec<NS>(L, prow_mine, i, out); }, nmsg,
                           [&](int q) { return slot_raw(L, prow_mine, q); }, loc, ms, mr);
@@ -1314,7 +1242,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
         STAMP(1);  // pair ring
         eval_chunk(done, cnt);
         STAMP(2);  // successor deltas, fingerprints, coverage, out-of-model invariants
-        if (!KSPLIT || (xflags & XF_ALL_SUCCESSORS)) {
+        if (!SYM || (xflags & XF_ALL_SUCCESSORS)) {
           resolve();  // the previous chunk's probes, after this chunk's arithmetic
           STAMP(3);
           issue_probe();
@@ -1356,7 +1284,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       gnext = take_group();
       gnn = shfl0_u64(gnext);
     }
-    while (KSPLIT && kpos - kdone + ccount > 0) {  // the group's last orbit keys (they key this group's rows)
+    while (SYM && kpos - kdone + ccount > 0) {  // the group's last orbit keys (they key this group's rows)
       const int kc = min(kpos - kdone, 64 - ccount);
       key_chunk(kdone, kc, kc == 0 || kpos - kdone + ccount <= 64);  // (the last chunk: every image left)
       kdone += kc;
@@ -1373,7 +1301,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       pfb = __hip_atomic_load(pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     drain();
-    if constexpr (!KSPLIT) STAMP(7);  // (non-symmetric builds: slot 7 = the group-end probe drain alone)
+    if constexpr (!SYM) STAMP(7);  // (non-symmetric builds: slot 7 = the group-end probe drain alone)
     build_all();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" ::"v"(pfa), "v"(pfb));

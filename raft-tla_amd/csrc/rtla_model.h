@@ -412,10 +412,7 @@ RTLA_HD uint32_t proj32(int i, uint32_t w0, uint32_t log) {
   h *= 0xC2B2AE3Du;
   return h ^ (h >> 16);
 }
-#ifndef RTLA_PROJ_OWNER
-#define RTLA_PROJ_OWNER 1  // 0: owner bits hashed like the rest (the round-5 fingerprint; A/B builds only)
-#endif
-constexpr uint64_t FP_HI = RTLA_PROJ_OWNER ? ~0xffffffffull : ~0ull;
+constexpr uint64_t FP_HI = ~0xffffffffull;  // the low half of .a is the owner's: server projections only
 // = hash_words(TAG_SRV << 8 | i, rec, SW), the tag's mixing folded to constants,
 // with the low half of .a replaced by the record's projection hash
 RTLA_HD FP h_srv(int i, const uint32_t* rec, int SW) {
@@ -425,7 +422,7 @@ RTLA_HD FP h_srv(int i, const uint32_t* rec, int SW) {
     s.a = mix_a(s.a ^ x);
     s.b = mix_b(s.b + x);
   }
-  if (RTLA_PROJ_OWNER) s.a = (s.a & FP_HI) | proj32(i, rec[0], rec[1]);
+  s.a = (s.a & FP_HI) | proj32(i, rec[0], rec[1]);
   return s;
 }
 // A message with its count, as its PACKED slot value (msg_pack: a bijection of
