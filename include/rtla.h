@@ -30,6 +30,16 @@
  *   rtla_expand_batch        TLC's Tool.getNextStates(Next, s) for a batch of
  *                            states: the parity seam used by the tests.
  *   rtla_state_text          TLC's state printer ("/\ var = value" lines).
+ *   rtla_simulate            TLC's -simulate [num=N] with -depth D and -seed S:
+ *                            random behaviours instead of exhaustive search --
+ *                            here started from the states of the BFS level
+ *                            last produced ({Init} after rtla_init: TLC's plain
+ *                            -simulate), so the search samples beyond the depth
+ *                            the frontier arena allows.
+ *   rtla_sim_replay,
+ *   rtla_sim_walk            the same walks recomputed on the host from
+ *                            (seed, walk id): reproduce one behaviour, as TLC
+ *                            does when rerun with the -seed it printed.
  *
  * Conventions: the caller owns host buffers, the library owns device memory.
  * Every function returns an int status (RTLA_OK = 0, >0 informational,
@@ -204,6 +214,63 @@ int rtla_orbit_key(const rtla_cfg *cfg, const uint32_t *row, uint64_t out[2], in
 int rtla_permute_row(const rtla_cfg *cfg, const uint32_t *row, const int *pi, uint32_t *out);
 const char *rtla_strerror(int status);
 int rtla_abi_version(void);
+
+/* Random-walk simulation (TLC -simulate / -depth / -seed).  Walk w -- a global
+ * 64-bit id: disjoint [first_walk, first_walk + n_walks) ranges of separate
+ * calls or processes compose -- starts at row w mod n of the current frontier
+ * (n states, numbered as rtla_frontier lists them) and takes up to `depth`
+ * steps (<= 65535).  At each step every action instance is evaluated in
+ * ascending instance number; every enabled successor counts as generated and
+ * is invariant-checked; if one violates, the walk ends with the violation
+ * (step, least violating instance); otherwise the walk moves to a uniformly
+ * drawn in-model successor (the draw depends on seed, w and the step only) or
+ * ends "stuck" when there is none.  Normative definition, shared by device and
+ * host: raft-tla_amd/csrc/rtla_sim.h.
+ * ends (may be NULL; 4 * n_walks u64): per walk the last state's fingerprint
+ * (2 words), a path digest over the states entered, steps taken | stop << 32
+ * (RTLA_SIM_STOP_*).  Walks run in batches of 2^18; no batch is started after
+ * one that found a violation (out->walks = walks run), and the violation
+ * reported is the least (walk, step, instance) -- independent of scheduling. */
+#define RTLA_SIM_STOP_DEPTH 0
+#define RTLA_SIM_STOP_STUCK 1
+#define RTLA_SIM_STOP_VIOLATION 2
+typedef struct {
+    uint64_t walks;        /* walks run */
+    uint64_t steps;        /* steps taken (states entered) */
+    uint64_t generated;    /* enabled successors evaluated (incl. out-of-model) */
+    uint64_t stuck;        /* walks that ended with no in-model successor */
+    double kernel_ms;      /* device time of the walks (rtla_sim_replay: host wall time) */
+    uint64_t viol_walk;    /* the violation, if status == RTLA_VIOLATION: walk id (else ~0), ... */
+    int32_t viol_step;     /* ... step (1-based) whose successor violates, ... */
+    int32_t viol_inst;     /* ... its action instance (-1: none), ... */
+    int32_t viol_mask;     /* ... the violated RTLA_INV_* and ... */
+    int32_t viol_in_model; /* ... whether that successor satisfies the StateConstraint */
+    int32_t status;        /* the call's return value */
+    int32_t flags;         /* on RTLA_E_SPEC / RTLA_E_OVERFLOW: RTLA_CAP_SPEC_ERROR / RTLA_CAP_ROW */
+    uint64_t taken[16];    /* steps taken per coverage code (rtla_coverage's numbering) */
+} rtla_sim_stats;
+/* On the GPU, from the context's current frontier.  Valid after rtla_init,
+ * rtla_step or rtla_recover on a single-shard context with world == 1 in
+ * RTLA_MODE_BFS whose frontier is not empty; anything else: RTLA_E_STATE.
+ * Touches neither the fingerprint set, the arena nor the BFS counters:
+ * rtla_step afterwards continues as if it had not run.  Returns RTLA_OK or
+ * RTLA_VIOLATION; after RTLA_VIOLATION, rtla_violation and rtla_trace report
+ * the simulated counterexample (the BFS parent chain from Init to the start
+ * row, the walk's states -- replayed on the host --, the violating successor)
+ * until the next rtla_simulate, rtla_step or rtla_reset. */
+int rtla_simulate(rtla_ctx *ctx, uint64_t seed, uint64_t first_walk, uint64_t n_walks, int32_t depth,
+                  uint64_t *ends, rtla_sim_stats *out);
+/* The same walks on the host from explicit start rows (n_start rows): no
+ * context, no GPU.  threads: 0 = the process's CPU allowance; at most 16. */
+int rtla_sim_replay(const rtla_cfg *cfg, const uint32_t *start_rows, size_t n_start, uint64_t seed,
+                    uint64_t first_walk, uint64_t n_walks, int32_t depth, int threads, uint64_t *ends,
+                    rtla_sim_stats *out);
+/* One walk from start_row on the host: the states it enters (not the start
+ * row) and, last, its violating successor if it ends in one (then returns
+ * RTLA_VIOLATION); labels = sub << 16 | instance, as rtla_trace.  *n_rows is
+ * set even if cap is too small (RTLA_E_ARG). */
+int rtla_sim_walk(const rtla_cfg *cfg, const uint32_t *start_row, uint64_t seed, uint64_t walk, int32_t depth,
+                  uint32_t *rows, int32_t *labels, size_t cap, size_t *n_rows);
 
 /* Diagnostic (performance analysis only): re-expand the current frontier
  * `reps` times with the level kernel's experiment switches `xflags` (XF_*

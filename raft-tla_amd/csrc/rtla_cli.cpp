@@ -5,6 +5,13 @@
 //     java tlc2.TLC [-workers W] [-coverage M] -config raft.cfg raft.tla
 // with
 //     rtla [-workers W] [-coverage M] [-gpus G] [-fpbits B] -config X.cfg SPEC.tla
+// and TLC's simulation mode (-simulate [num=N] -depth D -seed S) with
+//     rtla -simulate [num=N[,first=F]] [-depth D] [-seed S] [-bfs-levels K] -config X.cfg SPEC.tla
+// which runs K BFS levels (default 1: Init only, TLC's plain -simulate) and
+// then N random walks of up to D steps from the states of level K (walk w
+// starts at state w mod |level K|).  Walk ids are global: processes given
+// disjoint [F, F + N) ranges and the same seed explore disjoint walks, so a
+// large simulation can be split over GPUs by hand (-gpus > 1 is refused).
 //
 // SPEC.tla is either the reference's raft.tla (sha256 checked: the semantics
 // are compiled into the kernels, not parsed) or a wrapper module that
@@ -197,7 +204,11 @@ void usage() {
           "usage: rtla [-workers W] [-coverage M] [-gpus G] [-fpbits B] [-membudget BYTES] [-dump-levels]\n"
           "            [-raft PATH/raft.tla] [-skip-spec-check]\n"
           "            [-checkpoint MINUTES] [-checkpointdir PREFIX] [-recover PREFIX]\n"
-          "            -config FILE.cfg SPEC.tla\n");
+          "            [-simulate [num=N[,first=F]]] [-depth D] [-seed S] [-bfs-levels K]\n"
+          "            -config FILE.cfg SPEC.tla\n"
+          "  -simulate: after K BFS levels (default 1 = Init only) run N random walks (default 1000000) of up to\n"
+          "  D steps (default 100) from the states of level K; walk ids F .. F+N-1 are global, so runs with\n"
+          "  disjoint ranges and the same seed compose; one GPU only.\n");
 }
 
 std::string subst_names(const std::string& s, const std::vector<std::string>& servers,
@@ -338,6 +349,11 @@ int main(int argc, char** argv) {
   // TLC -checkpoint <minutes> / -recover <path> (the reference's .gitignore:2 states/ dir)
   double ckpt_minutes = 0;
   std::string ckpt_prefix = "states/ckpt", recover_prefix;
+  // TLC -simulate [num=N] / -depth D / -seed S, here from the states of BFS level -bfs-levels K
+  bool simulate = false;
+  uint64_t sim_num = 1000000, sim_first = 0, sim_seed = 0;
+  bool have_seed = false;
+  int sim_depth = 100, bfs_levels = 1;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -356,12 +372,36 @@ int main(int argc, char** argv) {
     else if (a == "-checkpoint") ckpt_minutes = atof(next().c_str());
     else if (a == "-checkpointdir") ckpt_prefix = next();
     else if (a == "-recover") recover_prefix = next();
+    else if (a == "-simulate") {
+      simulate = true;
+      if (i + 1 < argc && (!strncmp(argv[i + 1], "num=", 4) || !strncmp(argv[i + 1], "first=", 6))) {
+        std::stringstream opts(argv[++i]);
+        for (std::string kv; std::getline(opts, kv, ',');) {
+          if (kv.compare(0, 4, "num=") == 0) sim_num = strtoull(kv.c_str() + 4, nullptr, 10);
+          else if (kv.compare(0, 6, "first=") == 0) sim_first = strtoull(kv.c_str() + 6, nullptr, 10);
+          else { fprintf(stderr, "Error: -simulate: unknown option %s\n", kv.c_str()); return 255; }
+        }
+      }
+    }
+    else if (a == "-depth") sim_depth = atoi(next().c_str());
+    else if (a == "-seed") { sim_seed = strtoull(next().c_str(), nullptr, 10); have_seed = true; }
+    else if (a == "-bfs-levels") bfs_levels = atoi(next().c_str());
     else if (a == "-h" || a == "-help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { fprintf(stderr, "Error: unsupported option %s\n", a.c_str()); return 255; }
     else spec = a;
   }
   (void)workers;
   if (gpus < 1) { usage(); return 255; }
+  if (simulate && gpus > 1) {
+    fprintf(stderr, "Error: -simulate runs on one GPU; split the walks over processes instead "
+                    "(-simulate num=N,first=F with disjoint ranges and the same -seed)\n");
+    return 255;
+  }
+  if (simulate && (sim_depth < 0 || sim_depth > 65535 || bfs_levels < 1)) {
+    fprintf(stderr, "Error: -depth must be 0..65535 and -bfs-levels at least 1\n");
+    return 255;
+  }
+  if (simulate && !have_seed) sim_seed = (uint64_t)time(nullptr) ^ (uint64_t)getpid() << 32;  // printed, as TLC does
   if (gpus > 1 && !getenv("RTLA_RANK")) return launch_ranks(gpus, argv);
   const int rank = getenv("RTLA_RANK") ? atoi(getenv("RTLA_RANK")) : 0;
   const int world = getenv("RTLA_WORLD") ? atoi(getenv("RTLA_WORLD")) : 1;
@@ -517,7 +557,7 @@ int main(int argc, char** argv) {
   // everywhere: the clock is then the job's device time (the per-level
   // maximum over ranks, identical on every rank), not this rank's wall clock.
   double dev_s = 0, dev_ckpt = 0;
-  while (st == RTLA_OK) {
+  while (st == RTLA_OK && !(simulate && ls.level >= bfs_levels)) {
     st = rtla_step(ctx, &ls);
     if (st < 0) break;
     dev_s += ls.kernel_ms / 1e3;
@@ -556,6 +596,37 @@ int main(int argc, char** argv) {
     rtla_close(ctx);
     return 255;
   }
+  // -simulate: the BFS stopped at level K with nothing found (a BFS that
+  // finished or violated first is reported below as without -simulate)
+  bool simulated = false;
+  if (simulate && st == RTLA_OK) {
+    simulated = true;
+    size_t nfront = 0;
+    rtla_frontier(ctx, nullptr, 0, &nfront);
+    printf("Running Random Simulation with seed %llu from the %zu states of BFS level %d: %llu walks of depth %d "
+           "(walk ids %llu..%llu).\n",
+           (unsigned long long)sim_seed, nfront, ls.level, (unsigned long long)sim_num, sim_depth,
+           (unsigned long long)sim_first, (unsigned long long)(sim_first + sim_num - (sim_num ? 1 : 0)));
+    rtla_sim_stats ss;
+    memset(&ss, 0, sizeof ss);
+    st = rtla_simulate(ctx, sim_seed, sim_first, sim_num, sim_depth, nullptr, &ss);
+    if (st < 0) {
+      printf("Error: %s\n", rtla_strerror(st));
+      rtla_close(ctx);
+      return 255;
+    }
+    printf("Simulation: %llu walks, %llu steps taken, %llu states generated, %llu stuck; %.3f s on the GPU: "
+           "%.3g steps/s, %.3g generated/s.\n",
+           (unsigned long long)ss.walks, (unsigned long long)ss.steps, (unsigned long long)ss.generated,
+           (unsigned long long)ss.stuck, ss.kernel_ms / 1e3, ss.kernel_ms > 0 ? ss.steps / (ss.kernel_ms / 1e3) : 0.0,
+           ss.kernel_ms > 0 ? ss.generated / (ss.kernel_ms / 1e3) : 0.0);
+    if (st == RTLA_VIOLATION)
+      printf("Walk %llu (start state %llu of level %d) violates at step %d; rerun it with -seed %llu -simulate "
+             "num=1,first=%llu -depth %d -bfs-levels %d.\n",
+             (unsigned long long)ss.viol_walk, (unsigned long long)(nfront ? ss.viol_walk % nfront : 0), ls.level,
+             ss.viol_step, (unsigned long long)sim_seed, (unsigned long long)ss.viol_walk, ss.viol_step, ls.level);
+    secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
   int depth = 0;
   // depth = levels with new states; the last level returns new == 0 on DONE
   depth = st == RTLA_DONE ? ls.level - 1 : ls.level;
@@ -585,6 +656,9 @@ int main(int argc, char** argv) {
       }
     }
     exit_code = 12;
+  } else if (simulated) {
+    printf("Simulation completed. No error has been found in %d BFS levels and the walks above "
+           "(not an exhaustive search).\n", ls.level);
   } else {
     printf("Model checking completed. No error has been found.\n");
     printf("  Estimates of the probability that TLC did not check all reachable states\n"
@@ -608,9 +682,11 @@ int main(int argc, char** argv) {
     }
     printf("End of statistics.\n");
   }
-  printf("%llu states generated, %llu distinct states found, 0 states left on queue.\n",
-         (unsigned long long)ls.generated_total, (unsigned long long)ls.distinct_total);
-  printf("The depth of the complete state graph search is %d.\n", depth);
+  printf("%llu states generated, %llu distinct states found, %llu states left on queue.\n",
+         (unsigned long long)ls.generated_total, (unsigned long long)ls.distinct_total,
+         (unsigned long long)(simulated ? ls.new_states : 0));
+  if (simulated) printf("The depth of the breadth-first search before the simulation is %d.\n", depth);
+  else printf("The depth of the complete state graph search is %d.\n", depth);
   printf("Finished in %.2fs at (%s)\n", secs, now_str().c_str());
   rtla_close(ctx);
   return exit_code;

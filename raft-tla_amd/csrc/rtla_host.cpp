@@ -56,12 +56,14 @@
 #include <cstdio>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rtla.h"
 #include "rtla_device.h"
 #include "rtla_launch.h"
 #include "rtla_model.h"
+#include "rtla_sim.h"
 #include "rtla_synth.h"
 #include "rtla_text.h"
 
@@ -128,6 +130,19 @@ struct ShmComm {
   uint8_t* slot_at(int src, int dst, int world) const { return data + ((size_t)src * world + dst) * slot; }
 };
 
+// rtla_simulate's device buffers (allocated at first use, sized by the batch)
+// and the violation its last call found (rtla_violation / rtla_trace).
+struct SimState {
+  SimCounters* ctr = nullptr;
+  uint64_t* ends = nullptr;    // [ends_cap][4] end records of the batch
+  uint32_t* carry = nullptr;   // [carry_cap][W] current rows of a batch whose depth is split across launches
+  uint64_t ends_cap = 0, carry_cap = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool viol = false;
+  uint64_t seed = 0, walk = 0, start = 0;  // start: parent-record index of the walk's start row
+  int step = 0, inst = -1, mask = 0, in_model = 0;
+};
+
 // device scratch of the all-reduces: sums at [0, RED_MAX_AT), maxima after
 constexpr int RED_WORDS = 256, RED_MAX_AT = 192;
 
@@ -161,6 +176,7 @@ struct rtla_ctx {
   uint64_t max_front = 0;  // largest frontier of any shard in the job (multi-shard round count)
   int grid = 0;
   std::vector<uint32_t> init_row;
+  SimState sim;
 };
 
 // ---- the row arena as a ring (Ring, rtla_device.h)
@@ -824,6 +840,10 @@ extern "C" void rtla_close(rtla_ctx* x) {
   (void)hipSetDevice(x->device);
   for (auto& s : x->sh) free_shard(s);
   if (x->red) (void)hipFree(x->red);
+  for (void* p : {(void*)x->sim.ctr, (void*)x->sim.ends, (void*)x->sim.carry})
+    if (p) (void)hipFree(p);
+  if (x->sim.ev0) (void)hipEventDestroy(x->sim.ev0);
+  if (x->sim.ev1) (void)hipEventDestroy(x->sim.ev1);
   if (x->comm) ncclCommDestroy(x->comm);
   if (x->shm) {
     munmap(x->shm->hdr, x->shm->size);
@@ -1296,6 +1316,7 @@ extern "C" int rtla_recover(rtla_ctx* x, const char* prefix) {
   x->init_row.assign(x->L.W, 0);
   row_init(x->L, x->init_row.data());
   x->inited = true;
+  x->sim.viol = false;
   return RTLA_OK;
 }
 
@@ -1311,6 +1332,7 @@ extern "C" int rtla_reset(rtla_ctx* x) {
   }
   HIPCHK(hipStreamSynchronize(x->stream));
   x->inited = false; x->finished = false; x->level = 0; x->distinct = 0; x->generated = 0; x->max_front = 0;
+  x->sim.viol = false;
   return RTLA_OK;
 }
 
@@ -1683,6 +1705,7 @@ static void print_stamps(const DevCounters& c, int level) {
 extern "C" int rtla_step(rtla_ctx* x, rtla_level_stats* st) {
   if (!x) return RTLA_E_ARG;
   if (!x->inited || x->finished) return RTLA_E_STATE;
+  x->sim.viol = false;  // (a simulated violation is the last rtla_simulate's: the BFS goes on as if it had not run)
   double t0 = now_s();
   HIPCHK(hipSetDevice(x->device));
   const Layout& L = x->L;
@@ -1932,8 +1955,216 @@ static Shard* viol_shard(rtla_ctx* x) {  // violation found on a local shard
   return nullptr;
 }
 
+// ---- random-walk simulation (TLC -simulate; semantics: rtla_sim.h).  The
+// walks run on the device (k_simulate); the same walks are computed on the
+// host by sim_walk_serial: rtla_sim_replay / rtla_sim_walk (stateless, no
+// GPU), and the counterexample of a simulated violation (rtla_trace).
+template <class F>
+static auto sim_dispatch_n(const Layout& L, F f) {
+  switch (L.N) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 5>());
+  }
+}
+
+static bool sim_layout_ok(const Layout& L) { return L.fam[F_RECEIVE] + 3 * L.K <= SIM_MAX_CAND; }
+
+static void sim_fill_stats(rtla_sim_stats* st, uint64_t walks, const SimTally& t, uint64_t batch_first, double ms,
+                           int status) {
+  if (!st) return;
+  memset(st, 0, sizeof *st);
+  st->walks = walks; st->steps = t.steps; st->generated = t.generated; st->stuck = t.stuck;
+  st->kernel_ms = ms; st->status = status; st->flags = t.flags;
+  st->viol_walk = ~0ull; st->viol_inst = -1;
+  if (t.viol_key != SIM_NO_VIOLATION) {
+    st->viol_walk = batch_first + (t.viol_key >> 36);
+    st->viol_step = (int32_t)(t.viol_key >> 20 & 0xffff);
+    st->viol_inst = (int32_t)(t.viol_key >> 4 & 0xffff);
+    st->viol_in_model = (int32_t)(t.viol_key >> 3 & 1);
+    st->viol_mask = (int32_t)(t.viol_key & 7);
+  }
+  static_assert(sizeof st->taken / sizeof st->taken[0] == COVER_CODES, "rtla_sim_stats.taken holds every coverage code");
+  for (int k = 0; k < COVER_CODES; k++) st->taken[k] = t.taken[k];
+}
+
+// One walk's states (and, last, its violating successor) from the host.
+static int sim_walk_rows(const Layout& L, const uint32_t* start, uint64_t seed, uint64_t walk, int depth, uint32_t* rows,
+                         int32_t* labels, size_t cap, size_t* n_rows) {
+  if (!sim_layout_ok(L)) return RTLA_E_CONFIG;
+  std::vector<uint32_t> buf(2 * (size_t)L.W);
+  SimTally tl;
+  size_t n = 0;
+  const SimEnd e = sim_dispatch_n(L, [&](auto ns) {
+    return sim_walk_serial<decltype(ns)::value>(L, start, seed, walk, 0, depth, buf.data(), tl,
+                                                [&](int, const uint32_t* row, int32_t label, bool) {
+                                                  if (n < cap) {
+                                                    if (rows) memcpy(rows + n * L.W, row, (size_t)L.W * 4);
+                                                    if (labels) labels[n] = label;
+                                                  }
+                                                  n++;
+                                                });
+  });
+  if (n_rows) *n_rows = n;
+  if (tl.flags) return flags_to_status(tl.flags);
+  if ((rows || labels) && n > cap) return RTLA_E_ARG;
+  return e.stop == SIM_STOP_VIOLATION ? RTLA_VIOLATION : RTLA_OK;
+}
+
+extern "C" int rtla_sim_walk(const rtla_cfg* c, const uint32_t* start_row, uint64_t seed, uint64_t walk, int32_t depth,
+                             uint32_t* rows, int32_t* labels, size_t cap, size_t* n_rows) {
+  Layout L;
+  int r = layout_from_cfg(c, &L);
+  if (r) return r;
+  if (!start_row || depth < 0 || depth > SIM_MAX_DEPTH) return RTLA_E_ARG;
+  return sim_walk_rows(L, start_row, seed, walk, depth, rows, labels, cap, n_rows);
+}
+
+extern "C" int rtla_sim_replay(const rtla_cfg* c, const uint32_t* start_rows, size_t n_start, uint64_t seed,
+                               uint64_t first_walk, uint64_t n_walks, int32_t depth, int threads, uint64_t* ends,
+                               rtla_sim_stats* out) {
+  Layout L;
+  int r = layout_from_cfg(c, &L);
+  if (r) return r;
+  if (!start_rows || !n_start || depth < 0 || depth > SIM_MAX_DEPTH || first_walk + n_walks < first_walk)
+    return RTLA_E_ARG;
+  if (!sim_layout_ok(L)) return RTLA_E_CONFIG;
+  const double t0 = now_s();
+  const int nt = std::min(text_threads(threads), 16);
+  SimTally sum;
+  uint64_t done = 0, viol_first = 0;
+  // the same batches as rtla_simulate: no further batch after one that found a violation
+  for (uint64_t b0 = 0; b0 < n_walks && sum.viol_key == SIM_NO_VIOLATION; b0 += SIM_BATCH) {
+    const uint64_t nb = std::min<uint64_t>(SIM_BATCH, n_walks - b0);
+    std::vector<SimTally> part((size_t)nt);
+    std::atomic<uint64_t> next{0};
+    auto work = [&](int t) {
+      std::vector<uint32_t> buf(2 * (size_t)L.W);
+      SimTally& tl = part[(size_t)t];
+      for (;;) {
+        const uint64_t i0 = next.fetch_add(64);
+        if (i0 >= nb) break;
+        for (uint64_t i = i0; i < std::min(nb, i0 + 64); i++) {
+          const uint64_t w = first_walk + b0 + i;
+          const SimEnd e = sim_dispatch_n(L, [&](auto ns) {
+            return sim_walk_serial<decltype(ns)::value>(L, start_rows + (w % n_start) * (size_t)L.W, seed, w, i, depth,
+                                                        buf.data(), tl, [](int, const uint32_t*, int32_t, bool) {});
+          });
+          if (ends) {
+            uint64_t* o = ends + 4 * (b0 + i);
+            o[0] = e.last.a; o[1] = e.last.b; o[2] = e.digest; o[3] = sim_end_word(e.length, e.stop);
+          }
+        }
+      }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
+    work(0);
+    for (auto& th : pool) th.join();
+    for (const SimTally& p : part) {
+      sum.steps += p.steps; sum.generated += p.generated; sum.stuck += p.stuck; sum.flags |= p.flags;
+      sum.viol_key = std::min(sum.viol_key, p.viol_key);
+      for (int k = 0; k < COVER_CODES; k++) sum.taken[k] += p.taken[k];
+    }
+    viol_first = first_walk + b0;
+    done = b0 + nb;
+  }
+  const int status = sum.flags ? flags_to_status(sum.flags) : sum.viol_key != SIM_NO_VIOLATION ? RTLA_VIOLATION : RTLA_OK;
+  sim_fill_stats(out, done, sum, viol_first, (now_s() - t0) * 1e3, status);
+  return status;
+}
+
+extern "C" int rtla_simulate(rtla_ctx* x, uint64_t seed, uint64_t first_walk, uint64_t n_walks, int32_t depth,
+                             uint64_t* ends, rtla_sim_stats* out) {
+  if (!x) return RTLA_E_ARG;
+  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || viol_shard(x) ||
+      x->sh[0].n_cur == 0)
+    return RTLA_E_STATE;
+  if (depth < 0 || depth > SIM_MAX_DEPTH || first_walk + n_walks < first_walk) return RTLA_E_ARG;
+  const Layout& L = x->L;
+  if (!sim_layout_ok(L)) return RTLA_E_CONFIG;
+  HIPCHK(hipSetDevice(x->device));
+  Shard& s = x->sh[0];
+  SimState& m = x->sim;
+  m.viol = false;
+  if (!m.ctr) HIPCHK(hipMalloc((void**)&m.ctr, sizeof(SimCounters)));
+  if (!m.ev0) HIPCHK(hipEventCreate(&m.ev0));
+  if (!m.ev1) HIPCHK(hipEventCreate(&m.ev1));
+  const uint64_t batch = std::min<uint64_t>(SIM_BATCH, std::max<uint64_t>(1, n_walks));
+  if (m.ends_cap < batch) {
+    if (m.ends) (void)hipFree(m.ends);
+    m.ends = nullptr; m.ends_cap = 0;
+    HIPCHK(hipMalloc((void**)&m.ends, batch * 32));
+    m.ends_cap = batch;
+  }
+  SimTally sum;
+  double ms = 0;
+  uint64_t done = 0, viol_first = 0;
+  for (uint64_t b0 = 0; b0 < n_walks && sum.viol_key == SIM_NO_VIOLATION; b0 += SIM_BATCH) {
+    const uint64_t nb = std::min<uint64_t>(SIM_BATCH, n_walks - b0);
+    const int seg = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(depth, 1), SIM_LAUNCH_STEPS / nb));
+    if (seg < depth && m.carry_cap < nb) {
+      if (m.carry) (void)hipFree(m.carry);
+      m.carry = nullptr; m.carry_cap = 0;
+      HIPCHK(hipMalloc((void**)&m.carry, batch * (uint64_t)L.W * 4));
+      m.carry_cap = batch;
+    }
+    SimCounters h;
+    memset(&h, 0, sizeof h);
+    h.viol_key = SIM_NO_VIOLATION;
+    HIPCHK(hipMemcpyAsync(m.ctr, &h, sizeof h, hipMemcpyHostToDevice, x->stream));
+    HIPCHK(hipEventRecord(m.ev0, x->stream));
+    int t0 = 0;
+    do {  // (depth 0: one launch that writes the end records of the start rows)
+      const int t1 = std::min(depth, t0 + seg);
+      HIPCHK(launch_simulate(L, cur_ring(x, s), s.n_cur, seed, first_walk + b0, (uint32_t)nb, t0, t1, depth,
+                             seg < depth ? m.carry : nullptr, m.ends, m.ctr, x->stream));
+      t0 = t1;
+    } while (t0 < depth);
+    HIPCHK(hipEventRecord(m.ev1, x->stream));
+    HIPCHK(hipMemcpyAsync(&h, m.ctr, sizeof h, hipMemcpyDeviceToHost, x->stream));
+    if (ends) HIPCHK(hipMemcpyAsync(ends + 4 * b0, m.ends, nb * 32, hipMemcpyDeviceToHost, x->stream));
+    HIPCHK(hipStreamSynchronize(x->stream));
+    float bms = 0;
+    HIPCHK(hipEventElapsedTime(&bms, m.ev0, m.ev1));
+    ms += bms;
+    sum.steps += h.steps; sum.generated += h.generated; sum.stuck += h.stuck; sum.flags |= h.flags;
+    sum.viol_key = h.viol_key;
+    for (int k = 0; k < COVER_CODES; k++) sum.taken[k] += h.taken[k];
+    viol_first = first_walk + b0;
+    done = b0 + nb;
+    if (sum.flags) break;
+  }
+  int status = RTLA_OK;
+  if (sum.flags) {
+    report_flags(sum.flags);
+    status = flags_to_status(sum.flags);
+  } else if (sum.viol_key != SIM_NO_VIOLATION) {
+    status = RTLA_VIOLATION;
+  }
+  sim_fill_stats(out, done, sum, viol_first, ms, status);
+  if (status == RTLA_VIOLATION) {
+    m.viol = true;
+    m.seed = seed;
+    m.walk = viol_first + (sum.viol_key >> 36);
+    m.start = s.cur_base + m.walk % s.n_cur;
+    m.step = (int)(sum.viol_key >> 20 & 0xffff);
+    m.inst = (int)(sum.viol_key >> 4 & 0xffff);
+    m.in_model = (int)(sum.viol_key >> 3 & 1);
+    m.mask = (int)(sum.viol_key & 7);
+  }
+  return status;
+}
+
 extern "C" int rtla_violation(rtla_ctx* x, int32_t* inv_mask, int32_t* in_model) {
   if (!x) return RTLA_E_ARG;
+  if (x->sim.viol) {
+    if (inv_mask) *inv_mask = x->sim.mask;
+    if (in_model) *in_model = x->sim.in_model;
+    return RTLA_VIOLATION;
+  }
   Shard* s = viol_shard(x);
   if (inv_mask) *inv_mask = s ? s->viol_mask : 0;
   if (in_model) *in_model = s ? s->viol_in_model : 0;
@@ -2084,7 +2315,10 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
   Shard* vs = nullptr;
   for (auto& s : x->sh)
     if (s.viol_mask) { vs = &s; break; }
-  if (vs) {
+  const bool simv = x->sim.viol;  // (single shard, world 1: rtla_simulate's precondition)
+  if (simv) {
+    start[0] = 1; start[1] = 0; start[2] = x->sim.start; start[3] = 0;
+  } else if (vs) {
     start[0] = 1;
     start[1] = (uint64_t)vs->id;
     if (vs->viol_inst < 0) { start[2] = 0; start[3] = 0; }
@@ -2136,7 +2370,8 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
     g = (p >> 16) & ((1ull << 40) - 1);
   }
   std::reverse(insts.begin(), insts.end());
-  size_t n = insts.size() + 1;
+  // a simulated violation: the walk's states after the BFS chain, the violating successor last
+  size_t n = insts.size() + 1 + (simv ? (size_t)x->sim.step : 0);
   *n_rows = n;
   if (!rows && !labels) return RTLA_OK;
   if (n > cap) return RTLA_E_ARG;
@@ -2161,6 +2396,14 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
     if (labels) labels[k + 1] = (int32_t)(info[hit] & 0x7fffffffu);
   }
   (void)hipFree(d_row);
+  if (rc == RTLA_OK && simv) {  // replayed on the host from (seed, walk): no path is stored on the device
+    const size_t at = insts.size() + 1;
+    size_t got = 0;
+    rc = sim_walk_rows(L, row.data(), x->sim.seed, x->sim.walk, x->sim.step, rows ? rows + at * L.W : nullptr,
+                       labels ? labels + at : nullptr, n - at, &got);
+    if (rc == RTLA_VIOLATION && got == (size_t)x->sim.step) rc = RTLA_OK;
+    else if (rc >= 0) rc = RTLA_E_STATE;
+  }
   return rc;
 }
 

@@ -71,6 +71,13 @@ hipError_t launch_wave_expand(const Layout& L, const Ring& cur, uint64_t s_begin
                               const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap,
                               uint64_t* table, int tlog2, DevCounters* ctr, const ShardBox& box, int grid,
                               hipStream_t st);
+// Random walks from the frontier (rtla_ksim.hip, rtla_sim.h): walks [0, n_walks) of the batch starting at global
+// walk id `first`, steps t0 + 1 .. t1 of depth; carry (n_walks rows) only when the depth is split across launches.
+struct SimCounters;
+size_t simulate_lds_bytes(const Layout& L, int wpb);
+hipError_t launch_simulate(const Layout& L, const Ring& cur, uint64_t n_front, uint64_t seed, uint64_t first,
+                           uint32_t n_walks, int t0, int t1, int depth, uint32_t* carry, uint64_t* ends,
+                           SimCounters* ctr, hipStream_t st);
 hipError_t launch_insert_remote(const uint64_t* recv_fp, const uint64_t* counts, int nshard, uint64_t cap,
                                 uint64_t* table, int tlog2, uint32_t* ans, DevCounters* ctr, uint64_t max_count,
                                 hipStream_t st);

@@ -1,0 +1,167 @@
+// rtla_sim.h -- random-walk simulation (TLC's -simulate): the definitions the
+// kernel (rtla_ksim.hip) and the host replay (rtla_host.cpp) share, so both
+// compute the same walks bit for bit.
+//
+// Walk w (a global 64-bit id) starts at row w mod n of the n start rows (the
+// current BFS frontier; {Init} right after rtla_init).  Step t = 1..depth from
+// state s:
+//   * every action instance is evaluated in ascending instance number; each
+//     enabled successor counts as generated and is invariant-checked on
+//     parent + delta, as the BFS does for new and out-of-model successors;
+//   * a successor with a spec / row-capacity error raises the level kernels'
+//     flag (the call fails: a walk is never silently truncated);
+//   * if any successor violates an invariant the walk ends: its violation is
+//     (step t, least violating instance);
+//   * otherwise, with M the in-model successors in instance order, the walk
+//     ends "stuck" if M is empty, else it moves to M[draw(t, |M|)] -- draw is
+//     counter-based, a function of (seed, w, t) only -- materialised with the
+//     incremental fingerprint exactly as the level kernels do.
+// End record of a walk: 4 u64 = last state's fingerprint a, b | path digest
+// (sum mod 2^64 of sim_path_term over the states entered) | steps taken |
+// stop code << 32.
+#pragma once
+#include "rtla_device.h"
+#include "rtla_synth.h"
+
+namespace rtla {
+
+enum { SIM_STOP_DEPTH = 0, SIM_STOP_STUCK = 1, SIM_STOP_VIOLATION = 2 };
+constexpr int SIM_MAX_DEPTH = 65535;          // the step is a 16-bit field of the violation key
+constexpr uint64_t SIM_BATCH = 1ull << 18;    // walks per batch: no further batch after one that found a violation
+constexpr uint64_t SIM_LAUNCH_STEPS = 1ull << 23;  // walks x steps of one kernel launch, at most
+constexpr uint64_t SIM_NO_VIOLATION = ~0ull;
+constexpr int SIM_MAX_CAND = 512;             // candidates of one state, at most (fixed families + 3 per bag slot)
+
+// The walk's generator: its t-th below() call picks step t.
+RTLA_HD uint64_t sim_rng_base(uint64_t seed, uint64_t w) {
+  return mix_b(seed * 0x9E3779B97F4A7C15ull ^ mix_a(w + 0x243f6a8885a308d3ull));
+}
+RTLA_HD uint32_t sim_draw(uint64_t base, uint32_t t, uint32_t n) {  // t >= 1
+  SynthRng g{base, (uint64_t)t - 1};
+  return g.below(n);
+}
+
+// Path digest term of the state entered at step t.
+RTLA_HD uint64_t sim_path_term(FP f, uint32_t t) {
+  return mix_a(f.a ^ mix_b(f.b + (uint64_t)t * 0x9E3779B97F4A7C15ull));
+}
+
+RTLA_HD uint64_t sim_end_word(uint32_t length, int stop) { return (uint64_t)length | (uint64_t)stop << 32; }
+
+// Violation key, least first: walk (its index in the batch) << 36 | step << 20
+// | instance << 4 | in_model << 3 | violated-invariant mask.  The low four
+// bits are a function of (walk, step, instance), so the order is theirs.
+RTLA_HD uint64_t sim_viol_key(uint64_t rel_walk, uint32_t step, int inst, int in_model, int mask) {
+  return rel_walk << 36 | (uint64_t)step << 20 | (uint64_t)inst << 4 | (uint64_t)(in_model ? 8 : 0) | (uint64_t)(mask & 7);
+}
+
+RTLA_HD int sim_cover_code(const Layout& L, int inst, int sub) {  // the level kernels' cover_code
+  int fam = 0;
+  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
+  return fam == F_RECEIVE ? F_COUNT + sub : fam;
+}
+
+// Device counters of one rtla_simulate batch.
+struct SimCounters {
+  unsigned long long steps, generated, stuck;
+  unsigned long long viol_key;  // SIM_NO_VIOLATION, or the least sim_viol_key (atomicMin)
+  int flags, pad;
+  unsigned long long taken[COVER_CODES];
+};
+
+// Host tally of the same quantities.
+struct SimTally {
+  uint64_t steps = 0, generated = 0, stuck = 0;
+  uint64_t viol_key = SIM_NO_VIOLATION;
+  int flags = 0;
+  uint64_t taken[COVER_CODES] = {};
+};
+
+struct SimEnd {
+  FP last;
+  uint64_t digest;
+  uint32_t length;
+  int stop;
+  // stop == SIM_STOP_VIOLATION: the violation, at step length + 1
+  int viol_inst, viol_sub, viol_mask, viol_in_model;
+};
+
+// One walk on the host, serially.  buf: 2 * L.W words.  on_state(t, row,
+// label, violating) is called for every state entered (label = sub << 16 |
+// instance) and, on a violation, for the violating successor.  rel_walk: the
+// walk's index in its batch (violation key).
+template <int NS, class F>
+static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uint64_t seed, uint64_t w,
+                                     uint64_t rel_walk, int depth, uint32_t* buf, SimTally& tl, F on_state) {
+  constexpr int NR = NS ? NS : NMAX;
+  const int W = L.W;
+  uint32_t* cur = buf;
+  uint32_t* nxt = buf + W;
+  uint32_t pall[33];
+  uint16_t model[SIM_MAX_CAND];
+  for (int k = 0; k < W; k++) cur[k] = start[k];
+  const uint64_t base = sim_rng_base(seed, w);
+  SimEnd e{};
+  e.stop = SIM_STOP_DEPTH;
+  e.viol_inst = -1;
+  const int fixed = L.fam[F_RECEIVE];
+  for (int t = 1; t <= depth; t++) {
+    const FP pfp = fp_add(row_fp(cur), alllogs_delta<NS>(L, cur, pall));
+    const int nmsg = row_nmsg(L, cur);
+    const int ncand = fixed + 3 * nmsg;
+    auto inst_of = [&](int q) {
+      if (q < fixed) return q;
+      const int r = q - fixed, fam = r / nmsg;
+      return fam_base(L, F_RECEIVE + fam) + (r - fam * nmsg);
+    };
+    uint32_t total = 0;  // |M|; model[]: its instances, ascending
+    bool violated = false;
+    DeltaT<NR> d;
+    for (int q = 0; q < ncand; q++) {
+      const int inst = inst_of(q);
+      compute_delta<NS>(L, cur, inst, d);
+      if (!d.enabled) continue;
+      if (d.err) {
+        tl.flags |= d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW;
+        continue;
+      }
+      tl.generated++;
+      const int bad = check_invariants_v<NS>(L, cur, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
+      if (bad && !violated) {
+        violated = true;
+        e.viol_inst = inst; e.viol_sub = d.sub; e.viol_mask = bad; e.viol_in_model = d.in_model;
+        const FP cfp = fp_add(pfp, delta_fp<NS>(L, cur, d));
+        materialize<NS>(L, cur, d, pall, cfp, nxt);
+      }
+      if (d.in_model) model[total++] = (uint16_t)inst;
+    }
+    if (violated) {
+      e.stop = SIM_STOP_VIOLATION;
+      const uint64_t key = sim_viol_key(rel_walk, (uint32_t)t, e.viol_inst, e.viol_in_model, e.viol_mask);
+      if (key < tl.viol_key) tl.viol_key = key;
+      on_state(t, (const uint32_t*)nxt, (int32_t)(e.viol_sub << 16 | e.viol_inst), true);
+      break;
+    }
+    if (!total) {  // (not reachable from an in-model state of this spec: Restart is always enabled and stays in-model)
+      e.stop = SIM_STOP_STUCK;
+      tl.stuck++;
+      break;
+    }
+    {
+      const int inst = model[sim_draw(base, (uint32_t)t, total)];
+      compute_delta<NS>(L, cur, inst, d);
+      const FP cfp = fp_add(pfp, delta_fp<NS>(L, cur, d));
+      materialize<NS>(L, cur, d, pall, cfp, nxt);
+      e.digest += sim_path_term(cfp, (uint32_t)t);
+      tl.taken[sim_cover_code(L, inst, d.sub)]++;
+      tl.steps++;
+      e.length = (uint32_t)t;
+      on_state(t, (const uint32_t*)nxt, (int32_t)(d.sub << 16 | inst), false);
+    }
+    uint32_t* sw = cur; cur = nxt; nxt = sw;
+  }
+  e.last = row_fp(cur);
+  return e;
+}
+
+}  // namespace rtla

@@ -63,6 +63,13 @@ class _Stats(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class _SimStats(C.Structure):
+    _fields_ = [("walks", C.c_uint64), ("steps", C.c_uint64), ("generated", C.c_uint64), ("stuck", C.c_uint64),
+                ("kernel_ms", C.c_double), ("viol_walk", C.c_uint64), ("viol_step", C.c_int32),
+                ("viol_inst", C.c_int32), ("viol_mask", C.c_int32), ("viol_in_model", C.c_int32),
+                ("status", C.c_int32), ("flags", C.c_int32), ("taken", C.c_uint64 * 16)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("librtla.so not built at %s (run `make -C raft-tla_amd` or "
@@ -114,6 +121,12 @@ def _load():
         "rtla_rows_orbit_hash": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_int, P(C.c_uint64)]),
         "rtla_level_orbit_hash": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64)]),
         "rtla_orbit_text": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_char_p, C.c_size_t]),
+        "rtla_simulate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_uint64),
+                                    P(_SimStats)]),
+        "rtla_sim_replay": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64,
+                                      C.c_int32, C.c_int, P(C.c_uint64), P(_SimStats)]),
+        "rtla_sim_walk": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_uint64, C.c_uint64, C.c_int32, P(C.c_uint32),
+                                    P(C.c_int32), C.c_size_t, P(C.c_size_t)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -132,7 +145,7 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_synthetic_generate", "rtla_synthetic_dedup", "rtla_orbit_key", "rtla_permute_row",
             "rtla_rows_text_hash", "rtla_level_text_hash", "rtla_row_layout", "rtla_rows_orbit_hash",
             "rtla_level_orbit_hash", "rtla_orbit_text", "rtla_probe_bench3", "rtla_random_texts",
-            "rtla_frontier_rows"]
+            "rtla_frontier_rows", "rtla_simulate", "rtla_sim_replay", "rtla_sim_walk"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -195,6 +208,89 @@ class Result:
     trace: Optional[List[Tuple[str, str]]] = None   # (action label, state text)
     coverage: Optional[dict] = None
     seconds: float = 0.0
+
+
+SIM_STOP_DEPTH, SIM_STOP_STUCK, SIM_STOP_VIOLATION = 0, 1, 2
+SIM_SEED = 0x5AF72026  # default -seed of the random-walk simulation
+
+
+@dataclass
+class SimResult:
+    """One simulate() / sim_replay() call (rtla_sim_stats)."""
+    status: int = OK               # OK or VIOLATION
+    walks: int = 0                 # walks run (no batch of 2^18 is started after one that found a violation)
+    steps: int = 0                 # steps taken
+    generated: int = 0             # enabled successors evaluated
+    stuck: int = 0
+    kernel_ms: float = 0.0         # device time (sim_replay: host wall time)
+    violation: Optional[str] = None
+    viol_walk: Optional[int] = None
+    viol_step: int = 0             # 1-based step whose successor violates
+    viol_inst: int = -1
+    viol_mask: int = 0
+    viol_in_model: bool = True
+    taken: dict = field(default_factory=dict)   # steps taken per coverage name
+    ends: Optional[List[Tuple[int, int, int, int, int]]] = None  # per walk: (fp a, fp b, path digest, length, stop)
+
+
+def _sim_result(rc: int, st: _SimStats, ends, n: int) -> SimResult:
+    res = SimResult(status=rc, walks=st.walks, steps=st.steps, generated=st.generated, stuck=st.stuck,
+                    kernel_ms=st.kernel_ms, taken={COVER_NAMES[k]: st.taken[k] for k in range(len(COVER_NAMES))})
+    if rc == VIOLATION:
+        names = [nm for nm, b in INV_BITS.items() if st.viol_mask & b]
+        res.violation = names[0] if names else None
+        res.viol_walk, res.viol_step, res.viol_inst = st.viol_walk, st.viol_step, st.viol_inst
+        res.viol_mask, res.viol_in_model = st.viol_mask, bool(st.viol_in_model)
+    if ends is not None:
+        m = min(n, st.walks)
+        res.ends = [(ends[4 * k], ends[4 * k + 1], ends[4 * k + 2], ends[4 * k + 3] & 0xFFFFFFFF, ends[4 * k + 3] >> 32)
+                    for k in range(m)]
+    return res
+
+
+def _flat_rows(rows, w: int):
+    """(flat u32 array, #rows) of a list of rows -- or of rows already flat (Checker.frontier_flat)."""
+    if isinstance(rows, C.Array):
+        assert len(rows) % w == 0, "row width mismatch"
+        return rows, len(rows) // w
+    flat = (C.c_uint32 * max(1, len(rows) * w))()
+    for k, r in enumerate(rows):
+        assert len(r) == w, "row width mismatch"
+        flat[k * w:(k + 1) * w] = list(r)
+    return flat, len(rows)
+
+
+def sim_replay(cfg: Config, start_rows, n_walks: int, depth: int, seed: int = SIM_SEED,
+               first: int = 0, threads: int = 0, ends: bool = True) -> SimResult:
+    """Checker.simulate's walks recomputed on the host (rtla_sim_replay): walk
+    w starts at start_rows[w mod len(start_rows)] (a list of rows, or the flat
+    array of Checker.frontier_flat).  No GPU, no context."""
+    cc = cfg.c()
+    w = row_words(cfg)
+    flat, n_start = _flat_rows(start_rows, w)
+    buf = (C.c_uint64 * max(1, 4 * n_walks))() if ends else None
+    st = _SimStats()
+    rc = _lib.rtla_sim_replay(C.byref(cc), flat, n_start, seed, first, n_walks, depth, threads, buf,
+                              C.byref(st))
+    if rc < 0:
+        raise RtlaError(rc, "rtla_sim_replay", st.flags)
+    return _sim_result(rc, st, buf, n_walks)
+
+
+def sim_walk(cfg: Config, start_row: Sequence[int], walk: int, depth: int, seed: int = SIM_SEED):
+    """One walk from start_row on the host (rtla_sim_walk): (violating, steps)
+    with steps = [(instance, receive-sub, row)] of the states it enters and,
+    last when `violating`, of its violating successor."""
+    cc = cfg.c()
+    w = row_words(cfg)
+    arr = (C.c_uint32 * w)(*start_row)
+    cap = depth + 1
+    rows = (C.c_uint32 * (cap * w))()
+    labels = (C.c_int32 * cap)()
+    n = C.c_size_t(0)
+    rc = _check(_lib.rtla_sim_walk(C.byref(cc), arr, seed, walk, depth, rows, labels, cap, C.byref(n)), "rtla_sim_walk")
+    return rc == VIOLATION, [(labels[k] & 0xFFFF, (labels[k] >> 16) & 0x7FFF, list(rows[k * w:(k + 1) * w]))
+                             for k in range(n.value)]
 
 
 def _check(st: int, what: str):
@@ -485,6 +581,16 @@ class Checker:
         _check(_lib.rtla_frontier(self._h, buf, n.value, C.byref(n)), "rtla_frontier")
         return [list(buf[k * w:(k + 1) * w]) for k in range(n.value)]
 
+    def frontier_flat(self):
+        """The same rows as one flat ctypes u32 array (frontier_size() * row_words): a large level without a
+        Python list per state, e.g. as sim_replay's start rows."""
+        w = row_words(self.cfg)
+        n = C.c_size_t(0)
+        _check(_lib.rtla_frontier(self._h, None, 0, C.byref(n)), "rtla_frontier")
+        buf = (C.c_uint32 * (n.value * w))()
+        _check(_lib.rtla_frontier(self._h, buf, n.value, C.byref(n)), "rtla_frontier")
+        return buf
+
     def frontier_size(self) -> int:
         n = C.c_size_t(0)
         _check(_lib.rtla_frontier(self._h, None, 0, C.byref(n)), "rtla_frontier")
@@ -552,6 +658,18 @@ class Checker:
             raise RtlaError(rc, "rtla_synthetic_dedup", st.flags)
         return Level(0, st.frontier, st.new_states, st.generated, st.seconds, st.kernel_ms, st.probes, st.row_bytes,
                      st.expand_ms)
+
+    def simulate(self, n_walks: int, depth: int, seed: int = SIM_SEED, first: int = 0, ends: bool = False) -> SimResult:
+        """TLC -simulate: walks first .. first + n_walks - 1 of up to `depth`
+        steps from the states of the level last produced (walk w starts at
+        frontier row w mod frontier_size()).  The BFS is left untouched; after
+        a VIOLATION result, violation() and trace() give the counterexample."""
+        buf = (C.c_uint64 * max(1, 4 * n_walks))() if ends else None
+        st = _SimStats()
+        rc = _lib.rtla_simulate(self._h, seed, first, n_walks, depth, buf, C.byref(st))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_simulate", st.flags)
+        return _sim_result(rc, st, buf, n_walks)
 
     def coverage(self) -> dict:
         n = len(COVER_NAMES)
