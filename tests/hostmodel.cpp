@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rtla_model.h"
+#include "rtla_plan.h"
 
 using namespace rtla;
 
@@ -64,6 +65,36 @@ int hm_fingerprint(int n, int v, int t, int l, int c, int m, int k, int e, int i
   out[0] = f.a;
   out[1] = f.b;
   return 0;
+}
+
+// The multi-shard driver's level-end plans (rtla_plan.h).  Moves come back as
+// 5 words each; the count, -1 if the plan reports "full" (rehome), -2 if cap
+// is too small.  n (rehome) / m (rebalance): the counts after the moves.
+long hm_plan_rehome(int G, uint64_t rows_cap, const uint64_t* expm, const uint64_t* room, uint64_t* n, uint64_t* out,
+                    size_t cap) {
+  std::vector<uint64_t> nv(n, n + G);
+  std::vector<RehomeMove> mv;
+  const bool ok = plan_rehome(G, rows_cap, expm, room, nv, mv);
+  memcpy(n, nv.data(), 8 * (size_t)G);
+  if (!ok) return -1;
+  if (mv.size() > cap) return -2;
+  for (size_t k = 0; k < mv.size(); k++) {
+    const uint64_t v[5] = {(uint64_t)mv[k].a, (uint64_t)mv[k].b, (uint64_t)mv[k].dst, mv[k].base, mv[k].cnt};
+    memcpy(out + 5 * k, v, sizeof v);
+  }
+  return (long)mv.size();
+}
+
+long hm_plan_rebalance(int G, const uint64_t* n, uint64_t* m, uint64_t* out, size_t cap) {
+  std::vector<uint64_t> mv_after;
+  const std::vector<RebalanceMove> mv = plan_rebalance(G, std::vector<uint64_t>(n, n + G), mv_after);
+  memcpy(m, mv_after.data(), 8 * (size_t)G);
+  if (mv.size() > cap) return -2;
+  for (size_t k = 0; k < mv.size(); k++) {
+    const uint64_t v[5] = {(uint64_t)mv[k].a, (uint64_t)mv[k].b, mv[k].first, mv[k].base, mv[k].cnt};
+    memcpy(out + 5 * k, v, sizeof v);
+  }
+  return (long)mv.size();
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        deps = [SRC, os.path.join(CSRC, "rtla_model.h")]
+        deps = [SRC, os.path.join(CSRC, "rtla_model.h"), os.path.join(CSRC, "rtla_plan.h")]
         if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(OUT), exist_ok=True)
             subprocess.check_call(["g++", "-O2", "-std=c++20", "-shared", "-fPIC", "-I", CSRC, "-o", OUT + ".tmp", SRC])
@@ -28,6 +28,11 @@ def lib():
         _lib.hm_expand.argtypes = ints + [P(C.c_uint32), C.c_size_t, P(C.c_uint32), P(C.c_uint64), C.c_size_t]
         _lib.hm_expand.restype = C.c_long
         _lib.hm_fingerprint.argtypes = ints + [P(C.c_uint32), P(C.c_uint64)]
+        u64s = P(C.c_uint64)
+        _lib.hm_plan_rehome.argtypes = [C.c_int, C.c_uint64, u64s, u64s, u64s, u64s, C.c_size_t]
+        _lib.hm_plan_rehome.restype = C.c_long
+        _lib.hm_plan_rebalance.argtypes = [C.c_int, u64s, u64s, u64s, C.c_size_t]
+        _lib.hm_plan_rebalance.restype = C.c_long
     return _lib
 
 
@@ -62,3 +67,31 @@ def fingerprint(cfg, row):
     out = (C.c_uint64 * 2)()
     lib().hm_fingerprint(*_params(cfg), arr, out)
     return out[0], out[1]
+
+
+def _u64(vals):
+    return (C.c_uint64 * max(1, len(vals)))(*vals)
+
+
+def _moves(out, got):
+    return [tuple(out[5 * k:5 * k + 5]) for k in range(got)]
+
+
+def plan_rehome(G, rows_cap, expm, room, n):
+    """The driver's re-homing plan (rtla_plan.h): (moves, n after) with moves
+    as (a, b, dst, base, cnt), or (None, n after) when the plan reports full."""
+    cap = G * G
+    out, nn = (C.c_uint64 * (5 * cap))(), _u64(n)
+    got = lib().hm_plan_rehome(G, rows_cap, _u64([c for row in expm for c in row]), _u64(room), nn, out, cap)
+    assert got >= -1, got
+    return (None if got < 0 else _moves(out, got)), list(nn)[:G]
+
+
+def plan_rebalance(G, n):
+    """The driver's re-balancing plan: (moves, m) with moves as (a, b, first,
+    base, cnt) and m the shards' counts after them."""
+    cap = 2 * G
+    out, m = (C.c_uint64 * (5 * cap))(), _u64([0] * G)
+    got = lib().hm_plan_rebalance(G, _u64(n), m, out, cap)
+    assert got >= 0, got
+    return _moves(out, got), list(m)[:G]

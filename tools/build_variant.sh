@@ -11,14 +11,14 @@ H=/opt/rocm/bin/hipcc
 F="-O3 -std=c++20 -fPIC --offload-arch=gfx950 -Wno-unused-result $*"
 S=${SRC:-$ROOT/raft-tla_amd/csrc}  # SRC: a modified copy of csrc/ (its ../../include must hold rtla.h)
 ALL=${ALL_UNITS:-"rtla_kernels rtla_kwave rtla_kpack rtla_kspec_a rtla_kspec_b rtla_ksym_a rtla_ksym_b rtla_kgeneric_a rtla_kgeneric_b"}
+HOST="rtla_host rtla_comm rtla_ckpt rtla_simhost rtla_rows rtla_text"  # the host units (raft-tla_amd/Makefile HUNITS)
 pids=""
 if [ -n "$UNITS" ]; then
-  for u in $ALL rtla_host rtla_text; do cp $ROOT/raft-tla_amd/build/$u.o $D/$u.o; done
+  for u in $ALL $HOST; do cp $ROOT/raft-tla_amd/build/$u.o $D/$u.o; done
   for u in $UNITS; do $H $F -c -o $D/$u.o $S/$u.hip & pids="$pids $!"; done
 else
   for u in $ALL; do $H $F -c -o $D/$u.o $S/$u.hip & pids="$pids $!"; done
-  $H $F -c -o $D/rtla_host.o $S/rtla_host.cpp & pids="$pids $!"
-  $H $F -c -o $D/rtla_text.o $S/rtla_text.cpp & pids="$pids $!"
+  for u in $HOST; do $H $F -c -o $D/$u.o $S/$u.cpp & pids="$pids $!"; done
 fi
 for p in $pids; do wait $p || { echo "build_variant: a unit failed"; exit 1; }; done
 $H -shared -fPIC --offload-arch=gfx950 -o $D/librtla.so $D/*.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
