@@ -40,6 +40,29 @@ RTLA_HD int fp_owner(FP f, int nshard) {
   return (int)(((f.a & 0xffffffffull) * (unsigned long long)nshard) >> 32);
 }
 
+// ---- the three 64-bit records, each defined here alone.
+// Parent record of a stored state: shard << 56 | index << 16 | instance -- the
+// shard that holds its parent, the parent's index among that shard's parent
+// records (40 bits), the action instance that produced it.
+RTLA_HD uint64_t parent_record(uint64_t shard, uint64_t index, uint64_t inst) { return shard << 56 | index << 16 | inst; }
+RTLA_HD uint64_t parent_shard(uint64_t r) { return r >> 56; }
+RTLA_HD uint64_t parent_index(uint64_t r) { return (r >> 16) & ((1ull << 40) - 1); }
+RTLA_HD int parent_inst(uint64_t r) { return (int)(r & 0xffff); }
+// Successor record (rtla_expand_batch, ABI: include/rtla.h): input index << 32
+// | in_model << 31 | receive-sub << 16 | instance.  The low 31 bits are the
+// label rtla_trace returns.
+RTLA_HD uint64_t successor_info(uint64_t input, bool in_model, uint64_t sub, uint64_t inst) {
+  return input << 32 | (uint64_t)(in_model ? 1u : 0u) << 31 | sub << 16 | inst;
+}
+RTLA_HD uint64_t successor_input(uint64_t r) { return r >> 32; }
+RTLA_HD int successor_inst(uint64_t r) { return (int)(r & 0xffff); }
+RTLA_HD int32_t successor_label(uint64_t r) { return (int32_t)(r & 0x7fffffffu); }
+// Outbox ref of a queued successor (ShardBox::send_ref): parent's index in the
+// sender's current level << 16 | instance.
+RTLA_HD uint64_t outbox_ref(uint64_t parent, uint64_t inst) { return parent << 16 | inst; }
+RTLA_HD uint64_t outbox_parent(uint64_t r) { return r >> 16; }
+RTLA_HD int outbox_inst(uint64_t r) { return (int)(r & 0xffff); }
+
 // A BFS level's rows inside the shard's row arena.  The arena (`cap` rows, a
 // multiple of 64) is used as a ring: state g of the level is row
 // (start + g) mod cap.  The next level starts at the first multiple of 64 past
@@ -91,7 +114,7 @@ enum {
   XF_NO_SPECIAL = 4096,   // compact kernel: run-time layout even for a compiled-in configuration
   XF_DEDUP_ONLY = 8192,   // compact kernel: count new fingerprints, build no rows (synthetic microbench)
   XF_ALL_SUCCESSORS = 16384,  // compact kernel: no seen set -- every enabled successor (in-model or not) gets a
-                              // row, its record = input index << 32 | in_model << 31 | sub << 16 | instance
+                              // row, its record = successor_info(input index, in_model, sub, instance)
                               // (rtla_expand_batch: the parity seam runs the hot kernel)
 };
 

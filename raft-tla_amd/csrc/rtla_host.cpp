@@ -7,7 +7,8 @@
 // owns (fp_owner, rtla_device.h), the states it materialised (frontier double
 // buffer) and their parent pointers.  Device memory per shard:
 //   fingerprint set   2^fpset_log2 x 8 B   (open addressing, CAS insert)
-//   parents           one u64 per state: parent shard << 56 | parent index << 16 | instance
+//   parents           one u64 per state: its parent record (parent_record, rtla_device.h: the parent's shard in
+//                     bits 56-63, its index in bits 16-55, the action instance in bits 0-15)
 //   row arena         frontier_cap rows (a multiple of 64), used as a ring: the
 //                     current level's rows, then the next level's after them
 //   outbox / inbox    (multi-shard only) per destination: fingerprints, refs, answers
@@ -450,6 +451,12 @@ struct Level {
   double emax = 0.0;            // probe-kernel (k_expand_*) time of this level, ms
 };
 
+// Where local shard k's new states of the level go.
+static FrontierOut frontier_out(const rtla_ctx* x, const Level& lv, size_t k) {
+  const Shard& s = x->sh[k];
+  return FrontierOut{next_ring(x, s), s.parents, lv.next_base[k], lv.next_cap[k]};
+}
+
 // The row staging regions ([G][rows_cap][W + 2]): what s exports to peer p, what it received from p.
 static uint32_t* export_region(const rtla_ctx* x, const Shard& s, int p) {
   return s.send_rows + (uint64_t)p * x->rows_cap * ((uint64_t)x->L.W + 2);
@@ -509,8 +516,8 @@ static int unpack_staged(rtla_ctx* x, const Level& lv, size_t k, const uint32_t*
   const int G = x->nshard;
   HIPCHK(hipMemcpyAsync(s.rows_in, s.h_reb, 8 * G, hipMemcpyHostToDevice, x->stream));
   HIPCHK(hipMemcpyAsync(s.rows_base, s.h_reb + SHARD_MAX, 8 * G, hipMemcpyHostToDevice, x->stream));
-  HIPCHK(launch_unpack_rows(x->L.W, rows, s.rows_in, s.rows_base, G, x->rows_cap, next_ring(x, s), s.parents,
-                            lv.next_base[k], lv.next_cap[k], s.ctr, most, x->stream));
+  HIPCHK(launch_unpack_rows(x->L.W, rows, s.rows_in, s.rows_base, G, x->rows_cap, frontier_out(x, lv, k), s.ctr, most,
+                            x->stream));
   return RTLA_OK;
 }
 
@@ -667,12 +674,19 @@ static int level_setup(rtla_ctx* x, Level& lv) {
 // One shard: the whole level in one fused launch.
 static int launch_single(rtla_ctx* x, const Level& lv) {
   Shard& s = x->sh[0];
-  ShardBox box{1, 0, 0, 0, nullptr, nullptr, nullptr};
-  uint64_t blocks = (s.n_cur + 3) / 4;
-  int grid = (int)std::min<uint64_t>(blocks, (uint64_t)x->grid);
   HIPCHK(hipEventRecord(s.evm, x->stream));  // (re-recorded after the level kernel)
-  HIPCHK(launch_expand(x->L, cur_ring(x, s), 0, s.n_cur, s.cur_base, next_ring(x, s), s.parents, lv.next_base[0],
-                       lv.next_cap[0], s.table, x->tlog2, s.ctr, box, grid, x->stream, env_xflags(), nullptr, s.evm));
+  HIPCHK(launch_expand({.L = x->L,
+                        .cur = cur_ring(x, s),
+                        .s_end = s.n_cur,
+                        .cur_base = s.cur_base,
+                        .out = frontier_out(x, lv, 0),
+                        .table = s.table,
+                        .tlog2 = x->tlog2,
+                        .ctr = s.ctr,
+                        .st = x->stream,
+                        .xflags = env_xflags(),
+                        .grid = (int)std::min<uint64_t>((s.n_cur + 3) / 4, (uint64_t)x->grid)},
+                       s.evm));
   return RTLA_OK;
 }
 
@@ -721,13 +735,23 @@ static int exchange_rounds(rtla_ctx* x, Level& lv) {
       });
       const uint64_t b = s.pos, e = x->chunk ? std::min<uint64_t>(s.n_cur, b + x->chunk) : s.n_cur;
       if (e > b) {
-        uint64_t blocks = (e - b + 3) / 4;
-        int grid = (int)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), (uint64_t)x->grid);
         // RTLA_FAULT=launch:<rank> (tests): an actual launch fails
         if (round == 0 && fault_here(x, "launch")) local([&] { return launch_refused(x->stream); });
         local([&] {
-          return launch_expand(L, cur_ring(x, s), b, e, s.cur_base, next_ring(x, s), s.parents, lv.next_base[k],
-                               lv.next_cap[k], s.table, x->tlog2, s.ctr, box, grid, x->stream, env_xflags(), s.sent);
+          return launch_expand({.L = L,
+                                .cur = cur_ring(x, s),
+                                .s_begin = b,
+                                .s_end = e,
+                                .cur_base = s.cur_base,
+                                .out = frontier_out(x, lv, k),
+                                .table = s.table,
+                                .tlog2 = x->tlog2,
+                                .ctr = s.ctr,
+                                .box = box,
+                                .st = x->stream,
+                                .xflags = env_xflags(),
+                                .sent = s.sent,
+                                .grid = (int)std::min<uint64_t>((e - b + 3) / 4, (uint64_t)x->grid)});
         });
       }
       local([&] {
@@ -778,9 +802,21 @@ static int exchange_rounds(rtla_ctx* x, Level& lv) {
       Shard& s = x->sh[k];
       const uint64_t mx_out = *std::max_element(s.h_out.begin(), s.h_out.begin() + G);
       local([&] {
-        return launch_build_winners(L, cur_ring(x, s), s.cur_base, s.id, s.send_ref, s.send_ans, s.out_count, G,
-                                    x->box_cap, next_ring(x, s), s.parents, lv.next_base[k], lv.next_cap[k], s.ctr,
-                                    mx_out, s.send_rows, x->rehome ? x->rows_cap : 0, x->stream);
+        return launch_build_winners({.L = L,
+                                     .cur = cur_ring(x, s),
+                                     .cur_base = s.cur_base,
+                                     .me = s.id,
+                                     .send_ref = s.send_ref,
+                                     .ans = s.send_ans,
+                                     .counts = s.out_count,
+                                     .nshard = G,
+                                     .cap = x->box_cap,
+                                     .out = frontier_out(x, lv, k),
+                                     .ctr = s.ctr,
+                                     .max_count = mx_out,
+                                     .exp_rows = s.send_rows,
+                                     .exp_cap = x->rehome ? x->rows_cap : 0,
+                                     .st = x->stream});
       });
     }
     if (!left) break;
@@ -1102,8 +1138,8 @@ static int trace_start(rtla_ctx* x, bool bad, uint64_t start[4]) {
 }
 
 // Counterexample: find where it starts (trace_start), walk the parent records
-// back to Init -- across shards: a record is shard << 56 | index << 16 |
-// instance -- then replay the action instances forward from the Init row with
+// back to Init -- across shards: a record names its parent's shard
+// (parent_record, rtla_device.h) -- then replay the action instances forward from the Init row with
 // the kernel that built them.  Collective when world > 1 (every rank calls it;
 // each step's record comes from the rank that holds it).
 extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t cap, size_t* n_rows) {
@@ -1123,9 +1159,9 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
     uint64_t p = 0;
     if (int rc = comm_parent_record(x, shard, g, bad, &p)) return rc;
     if (p == ~0ull) break;  // Init
-    insts.push_back((int32_t)(p & 0xffff));
-    shard = p >> 56;
-    g = (p >> 16) & ((1ull << 40) - 1);
+    insts.push_back(parent_inst(p));
+    shard = parent_shard(p);
+    g = parent_index(p);
   }
   std::reverse(insts.begin(), insts.end());
   // a simulated violation: the walk's states after the BFS chain, the violating successor last
@@ -1147,11 +1183,11 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
     if (r < 0) { rc = r; break; }
     size_t hit = info.size();
     for (size_t q = 0; q < info.size(); q++)
-      if ((int32_t)(info[q] & 0xffff) == insts[k]) hit = q;
+      if (successor_inst(info[q]) == insts[k]) hit = q;
     if (hit == info.size()) { rc = RTLA_E_STATE; break; }
     memcpy(row.data(), &out[hit * L.W], L.W * 4);
     if (rows) memcpy(rows + (k + 1) * L.W, row.data(), L.W * 4);
-    if (labels) labels[k + 1] = (int32_t)(info[hit] & 0x7fffffffu);
+    if (labels) labels[k + 1] = successor_label(info[hit]);
   }
   (void)hipFree(d_row);
   if (rc == RTLA_OK && simv) {  // replayed on the host from (seed, walk): no path is stored on the device

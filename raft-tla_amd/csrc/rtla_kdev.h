@@ -1,0 +1,460 @@
+// rtla_kdev.h -- the device helpers every kernel translation unit shares
+// (and the few host helpers of their launchers): wave and lane primitives,
+// LDS copies, ring stores, the fingerprint set, flags and violations,
+// next-level and outbox reservations, candidates and coverage, the
+// wave-per-state kernels' per-parent setup, SYMMETRY's successor accessors,
+// the compiled-in layouts.  The level kernel itself is rtla_klevel.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+
+#include <algorithm>
+
+#include "rtla_device.h"
+
+#include "rtla_model.h"
+#include "rtla_synth.h"
+#include "rtla_launch.h"
+
+using namespace rtla;
+
+namespace {
+
+// ---- wave and lane primitives
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// (the readlane builtins return a signed int: widen through uint32_t)
+__device__ __forceinline__ unsigned long long shfl0_u64(unsigned long long v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return (unsigned long long)lo | (unsigned long long)hi << 32;
+}
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+  return (unsigned long long)lo | (unsigned long long)hi << 32;
+}
+__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+  return (unsigned long long)lo | (unsigned long long)hi << 32;
+}
+__device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
+  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo |= (uint32_t)__shfl_xor((int)lo, o);
+    hi |= (uint32_t)__shfl_xor((int)hi, o);
+  }
+  return (unsigned long long)lo | (unsigned long long)hi << 32;
+}
+
+// ---- LDS layouts, copies and ring stores
+
+constexpr int STAGE_ROWS = 16;  // LDS staging rows per wave
+
+struct LaneWords {  // word w of a per-lane array kept word-major (stride 64: bank-conflict free)
+  uint32_t* p;
+  __device__ __forceinline__ uint32_t& operator[](int w) const { return p[w * 64]; }
+};
+template <int S>
+struct StridedWords {  // the same with stride S (one array per state of an S-state group)
+  uint32_t* p;
+  __device__ __forceinline__ uint32_t& operator[](int w) const { return p[w * S]; }
+};
+// Per-wave LDS of the lane-per-state row builders: 64 rows | their allLogs' words.
+__host__ __device__ constexpr int lane_lds_words(int W, int AW) { return 64 * W + 64 * AW; }
+
+// Per-wave LDS of the wave-per-state kernels: parent row (W, padded to even) |
+// new allLogs words (32) | parent server-record hashes (NMAX FPs = 4 * NMAX
+// words, 8-byte aligned) | staging rows (STAGE_ROWS * W).  The per-wave block
+// is a multiple of 4 words so every wave's hash slots stay 8-byte aligned.
+__host__ __device__ constexpr int even_words(int W) { return (W + 1) & ~1; }
+__host__ __device__ constexpr int wave_lds_words(int W) {
+  return (even_words(W) + 32 + 4 * NMAX + STAGE_ROWS * W + 3) & ~3;
+}
+struct WaveLds {
+  uint32_t* prow;
+  uint32_t* pall;
+  FP* hsrv;
+  uint32_t* stage;
+};
+__device__ __forceinline__ WaveLds wave_lds(uint32_t* lds, int wave, int W) {
+  uint32_t* prow = lds + wave * wave_lds_words(W);
+  uint32_t* pall = prow + even_words(W);
+  return WaveLds{prow, pall, reinterpret_cast<FP*>(pall + 32), pall + 32 + 4 * NMAX};
+}
+
+// Copy n contiguous words global -> LDS (dst and src 16-byte aligned) with 8
+// 16-byte loads in flight per lane (a plain loop waits for every load before
+// its LDS store).
+__device__ __forceinline__ void copy_words_lds16(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int n,
+                                                 int lane) {
+  const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
+  uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
+  const int n4 = n >> 2;
+  int w = lane;
+  for (; w + 7 * 64 < n4; w += 8 * 64) {
+    uint4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = s4[w + j * 64];
+#pragma unroll
+    for (int j = 0; j < 8; j++) d4[w + j * 64] = v[j];
+  }
+  for (; w < n4; w += 64) d4[w] = s4[w];
+  for (int t = (n4 << 2) + lane; t < n; t += 64) dst[t] = src[t];
+}
+
+// Gather nv rows of W words (row r from src_row(r), a wave-uniform address)
+// into LDS rows dst + r * W: lane l moves words l, l + 64, ... of each row,
+// 8 rows (8 loads per lane) in flight.
+template <class F>
+__device__ __forceinline__ void gather_rows_lds(uint32_t* __restrict__ dst, int W, int nv, F src_row, int lane) {
+  for (int r0 = 0; r0 < nv; r0 += 8) {
+    for (int c = lane; c < W; c += 64) {
+      uint32_t v[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) v[j] = r0 + j < nv ? src_row(r0 + j)[c] : 0u;
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        if (r0 + j < nv) dst[(r0 + j) * W + c] = v[j];
+    }
+  }
+}
+
+// Row pointer of state g of a level (see Ring, rtla_device.h).
+__device__ __forceinline__ uint32_t* ring_row(const Ring& R, unsigned long long g, int W) {
+  return R.base + ring_idx(R, g) * (unsigned long long)W;
+}
+
+// Store nr consecutive rows (LDS src, W words each) as states g .. g + nr - 1
+// of the level R, coalesced; the range may wrap at the end of the arena.
+__device__ __forceinline__ void store_rows_ring(const Ring& R, unsigned long long g, int nr, int W,
+                                                const uint32_t* __restrict__ src, int lane) {
+  const unsigned long long p = ring_idx(R, g);
+  const int n1 = (int)min<unsigned long long>(R.cap - p, (unsigned long long)nr) * W;  // words before the wrap
+  uint32_t* d1 = R.base + p * (unsigned long long)W;
+  const int nw = nr * W;
+  for (int w = lane; w < nw; w += 64) {
+    if (w < n1) d1[w] = src[w];
+    else R.base[w - n1] = src[w];
+  }
+}
+
+// ---- flags, violations, the block's coverage tally
+
+__device__ __forceinline__ void set_flag(DevCounters* c, int f) { atomicOr(&c->flags, f); }
+
+// RTLA_CHECKED builds: every global row / parent-record index is checked
+// against the buffer capacities the host stores in DevCounters; a bad index
+// raises FLAG_BAD_INDEX (reported by rtla_step) instead of faulting.
+#ifdef RTLA_CHECKED
+#define RTLA_IDX_OK(ctr, idx, cap) ((idx) < (cap) ? true : (set_flag((ctr), FLAG_BAD_INDEX), false))
+#else
+#define RTLA_IDX_OK(ctr, idx, cap) true
+#endif
+
+// An enabled successor whose Delta reports an evaluation error (err 1: TLC
+// evaluation error, else: row capacity) raises its flag and is dropped.
+// Returns whether the successor still counts.
+__device__ __forceinline__ bool enabled_ok(int* flags, bool en, int err) {
+  if (en && err) {
+    atomicOr(flags, err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW);
+    en = false;
+  }
+  return en;
+}
+
+// The first violation found wins and is never replaced.  Called by the whole
+// wave (bad = this lane's violated-invariant mask, 0 if none): one CAS per
+// wave -- its first violating lane -- and none once a violation has been
+// recorded, so successors that all violate an invariant (random states, or
+// a violation reached by many parents) do not serialise on that one word.
+// Returns true on the lane whose violation was recorded.
+__device__ __forceinline__ bool claim_violation(DevCounters* c, int bad, int lane) {
+  const unsigned long long m = __ballot(bad != 0);
+  if (!m) return false;
+  if (lane != __builtin_ctzll(m)) return false;
+  if (__hip_atomic_load(&c->viol_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
+  return atomicCAS(&c->viol_mask, 0, bad) == 0;
+}
+// The same claim by one lane on its own (callers under a divergent mask: no ballot).
+__device__ __forceinline__ bool claim_violation_lane(DevCounters* c, int bad) {
+  return bad && __hip_atomic_load(&c->viol_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 &&
+         atomicCAS(&c->viol_mask, 0, bad) == 0;
+}
+// After a successful claim: what violated (child = ~0: the successor has no row).
+__device__ __forceinline__ void record_violation(DevCounters* c, unsigned long long parent, int inst, int in_model,
+                                                 unsigned long long child) {
+  c->viol_parent = parent;
+  c->viol_inst = inst;
+  c->viol_in_model = in_model;
+  c->viol_child = child;
+}
+
+// The block's coverage tally (n __shared__ counters): zeroed at kernel start,
+// added to the device counters at its end.  Both called by every thread.
+__device__ __forceinline__ void cover_zero(unsigned int* cov, int n) {
+  for (int k = threadIdx.x; k < n; k += blockDim.x) cov[k] = 0;
+  __syncthreads();
+}
+__device__ __forceinline__ void cover_flush(const unsigned int* cov, int n, unsigned long long* total) {
+  __syncthreads();
+  for (int k = threadIdx.x; k < n; k += blockDim.x)
+    if (cov[k]) atomicAdd(&total[k], (unsigned long long)cov[k]);
+}
+
+// ---- the fingerprint set
+
+// Insert into the fingerprint set.  1 = newly inserted, 0 = already present,
+// -1 = probe limit exceeded (set too full).  Slots only ever change 0 -> key;
+// the CAS both tests and claims a slot, so every probe is one round trip.
+__device__ __forceinline__ int fpset_insert(unsigned long long* table, int log2, FP f) {
+  const unsigned long long key = f.b | 1ull;
+  const unsigned long long mask = (1ull << log2) - 1ull;
+  unsigned long long idx = f.a >> (64 - log2);
+  for (int probe = 0; probe < 4096; probe++) {
+    unsigned long long old = atomicCAS(&table[idx], 0ull, key);
+    if (old == 0ull) return 1;
+    if (old == key) return 0;
+    idx = (idx + 1ull) & mask;
+  }
+  return -1;
+}
+
+// Finish an insert whose home slot `idx` was READ (not CAS'd) as `seen`.
+// Slots only ever change 0 -> key, so a slot holding the key proves the
+// state is present, and one holding another key can be skipped for good;
+// only an empty slot needs the CAS (which may then find the key after all).
+__device__ __forceinline__ bool fpset_resolve_loaded(unsigned long long* table, int log2, unsigned long long key,
+                                                     unsigned long long idx, unsigned long long seen,
+                                                     DevCounters* ctr) {
+  const unsigned long long mask = (1ull << log2) - 1ull;
+  for (int probe = 1;; probe++) {
+    if (seen == key) return false;
+    if (seen == 0ull) {
+      seen = atomicCAS(&table[idx], 0ull, key);
+      if (seen == 0ull) return true;
+      if (seen == key) return false;
+    }
+    if (probe >= 4096) {
+      set_flag(ctr, FLAG_FPSET_FULL);
+      return false;
+    }
+    idx = (idx + 1ull) & mask;
+    seen = __hip_atomic_load(&table[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Finish an insert whose first CAS (at home slot `idx`) returned `old`:
+// continue linear probing while the slot holds another key.  true = new.
+__device__ __forceinline__ bool fpset_resolve(unsigned long long* table, int log2, unsigned long long key,
+                                              unsigned long long idx, unsigned long long old, DevCounters* ctr) {
+  const unsigned long long mask = (1ull << log2) - 1ull;
+  for (int probe = 1; old != 0ull && old != key; probe++) {
+    if (probe >= 4096) {
+      set_flag(ctr, FLAG_FPSET_FULL);
+      return false;
+    }
+    idx = (idx + 1ull) & mask;
+    old = atomicCAS(&table[idx], 0ull, key);
+  }
+  return old == 0ull;
+}
+
+// ---- reservations: next-level rows, outbox records
+
+// n rows for the whole wave from `counter` (one atomic, by lane 0): returns
+// the first, on every lane.  A reservation that ends past `cap` raises
+// FLAG_FRONTIER_FULL; what the caller then does with the rows that fit is
+// its own business.
+__device__ __forceinline__ unsigned long long reserve_rows(unsigned long long* counter, int n, unsigned long long cap,
+                                                           DevCounters* ctr, int lane) {
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(counter, (unsigned long long)n);
+  base = shfl0_u64(base);
+  if (base + n > cap && lane == 0) set_flag(ctr, FLAG_FRONTIER_FULL);
+  return base;
+}
+
+// Record (f, ref) into slot `slot` (< box.cap) of owner's outbox region.
+__device__ __forceinline__ void outbox_put(const ShardBox& box, int owner, unsigned long long slot, FP f,
+                                           unsigned long long ref) {
+  const unsigned long long k = (unsigned long long)owner * box.cap + slot;
+  box.send_fp[2 * k] = f.a;
+  box.send_fp[2 * k + 1] = f.b;
+  box.send_ref[k] = ref;
+}
+// The lanes with `ov` append their record to the overflow list (whole wave:
+// one atomic on its counter); a full list raises FLAG_OUTBOX_FULL.
+__device__ __forceinline__ void overflow_put(const ShardBox& box, bool ov, FP f, unsigned long long ref,
+                                             DevCounters* ctr, int lane) {
+  const unsigned long long om = __ballot(ov);
+  if (!om) return;
+  unsigned long long ob = 0;
+  if (lane == 0) ob = atomicAdd(box.over_count, (unsigned long long)__popcll(om));
+  ob = shfl0_u64(ob);
+  if (ov) {
+    const unsigned long long k = ob + __popcll(om & ((1ull << lane) - 1ull));
+    if (k < box.over_cap) {
+      box.over_fp[2 * k] = f.a;
+      box.over_fp[2 * k + 1] = f.b;
+      box.over_ref[k] = ref;
+    } else {
+      set_flag(ctr, FLAG_OUTBOX_FULL);
+    }
+  }
+}
+
+// ---- candidates and coverage codes
+
+// Map the q-th candidate of a parent with `nmsg` bag slots to an instance id:
+// the fixed families first, then Receive / Duplicate / Drop over used slots.
+__device__ __forceinline__ int candidate_inst(const Layout& L, int q, int nmsg) {
+  const int fixed = L.fam[F_RECEIVE];
+  if (q < fixed) return q;
+  int r = q - fixed;
+  int fam = r / nmsg, slot = r - fam * nmsg;
+  return fam_base(L, F_RECEIVE + fam) + slot;
+}
+
+__device__ __forceinline__ int inst_family(const Layout& L, int inst) {
+  int fam = 0;
+#pragma unroll
+  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
+  return fam;
+}
+
+__device__ __forceinline__ int cover_code(const Layout& L, int inst, int sub) {
+  const int fam = inst_family(L, inst);
+  return fam == F_RECEIVE ? F_COUNT + sub : fam;
+}
+
+// ---- per-parent setup of the wave-per-state kernels
+
+// The per-parent data every lane needs, from the parent row in LDS: lanes
+// < NS hash its server records (hsrv), lane NS derives allLogs' (pall).
+// Returns the parent fingerprint with allLogs' already applied.
+template <int NS>
+__device__ __forceinline__ FP parent_setup(const Layout& L, const uint32_t* row, uint32_t* pall, FP* hsrv, int lane) {
+  FP afp{0, 0};
+  if (lane < NS) {
+    uint32_t rec[3 + NS];
+    load_rec<NS>(L, row, lane, rec);
+    hsrv[lane] = h_srv(lane, rec, 3 + NS);
+  } else if (lane == NS) {
+    afp = alllogs_delta<NS>(L, row, pall);
+  }
+  afp.a = readlane_u64(afp.a, NS);
+  afp.b = readlane_u64(afp.b, NS);
+  wave_sync();
+  return fp_add(row_fp(row), afp);
+}
+// Load the parent row into LDS, then parent_setup.
+template <int NS>
+__device__ __forceinline__ FP load_parent(const Layout& L, const uint32_t* __restrict__ src, uint32_t* prow,
+                                          uint32_t* pall, FP* hsrv, int lane) {
+  const int W = L.W;
+  for (int w = lane; w < W; w += 64) prow[w] = src[w];
+  wave_sync();
+  return parent_setup<NS>(L, prow, pall, hsrv, lane);
+}
+
+// ---- SYMMETRY
+
+// The successor parent + d through sym_key's accessors (server records, bag
+// slots, election records), without materialising it:
+// f(rec_of, nmsg, slot_of, nelec, elec_of).
+template <int NS, class P, class F>
+__device__ __forceinline__ auto with_successor(const Layout& L, P prow, const DeltaT<NS>& d, F f) {
+  constexpr int EW = 2 + NS;
+  const int ne0 = row_nelec(L, prow);
+  auto rec_of = [&](int i, uint32_t* out) {
+    load_rec<NS>(L, prow, i, out);
+    if (i == d.srv) {
+#pragma unroll
+      for (int w = 0; w < 3 + NS; w++) out[w] = d.rec[w];
+    }
+  };
+  auto slot_of = [&](int q) { return bag_get(L, prow, d, q); };
+  auto elec_of = [&](int e, uint32_t* out) {
+    if (e < ne0) {
+      out[0] = elec_w0(L, prow, e);
+      out[1] = elec_log(L, prow, e);
+#pragma unroll
+      for (int j = 0; j < NS; j++) out[2 + j] = elec_vl(L, prow, e, j);
+    } else {
+#pragma unroll
+      for (int w = 0; w < EW; w++) out[w] = d.erec[w];
+    }
+  };
+  return f(rec_of, d.nmsg, slot_of, ne0 + (d.elec ? 1 : 0), elec_of);
+}
+// Orbit key of the successor parent + d (allLogs' fingerprint afp).
+template <int NS, class P>
+__device__ __forceinline__ FP successor_orbit_key(const Layout& L, P prow, const DeltaT<NS>& d, FP afp) {
+  return with_successor<NS>(L, prow, d, [&](auto rec_of, int nmsg, auto slot_of, int nelec, auto elec_of) {
+    return sym_key<NS>(L, rec_of, nmsg, slot_of, nelec, elec_of, afp);
+  });
+}
+
+// ---- compiled-in layouts
+
+// The layout a kernel runs on: the run-time argument, or (LC.N != 0) the
+// configuration compiled in as a template parameter, whose fields the
+// compiler then folds into every offset, bound and loop of the model code.
+template <Layout LC>
+__device__ __forceinline__ const Layout& pick_layout(const Layout& rt) {
+  if constexpr (LC.N == 0) return rt;
+  else return LC;
+}
+
+// Configurations whose layout is compiled into k_expand_compact and
+// k_build_winners (the BASELINE workloads bench.py runs); any other
+// configuration runs the same kernels on its run-time layout.
+namespace specs {
+constexpr Layout CFG2 = layout_of(3, 2, 3, 2, 1, 0, 18, 6, INV_ELECTION_SAFETY | INV_LOG_MATCHING);  // configs[1]
+constexpr Layout CFG1 = layout_of(3, 1, 2, 1, 1, 0, 24, 3, INV_NO_TWO_LEADERS);                     // configs[0]
+constexpr Layout EXHAUST = layout_of(3, 2, 2, 2, 1, 2, 3, 3, INV_ELECTION_SAFETY | INV_LOG_MATCHING);
+constexpr Layout CFG3 = layout_of(3, 2, 4, 3, 2, 0, 20, 9, 0);                                      // configs[2]
+constexpr Layout SYNTH = layout_of(3, 2, 4, 3, 2, 0, 12, 9, INV_ELECTION_SAFETY | INV_LOG_MATCHING);  // configs[4]
+constexpr Layout symmetric(Layout l) {
+  l.sym = 1;
+  return l;
+}
+constexpr Layout CFG4 = symmetric(layout_of(5, 1, 3, 2, 1, 0, 20, 10, 0));  // configs[3], SYMMETRY
+static_assert(CFG2.N == 3 && CFG1.N == 3 && EXHAUST.N == 3 && CFG3.N == 3 && SYNTH.N == 3 && CFG4.N == 5,
+              "compiled-in layouts must be valid");
+}  // namespace specs
+
+// ---- launch helpers (host)
+
+#define RTLA_DISPATCH_N(L, KERNEL, ...)                        \
+  switch ((L).N) {                                             \
+    case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break; \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break; \
+    case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break; \
+    case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break; \
+  }
+
+inline unsigned grid_x(uint64_t n, int per_block) {
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, 4096));
+}
+
+inline int device_cus() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+  }
+  return cus;
+}
+
+}  // namespace

@@ -2,13 +2,13 @@
 // BFS hot path on gfx950.
 //
 // One BFS level on one shard = one launch of k_expand_compact
-// (rtla_kernels_common.h), picked here by layout from
+// (rtla_klevel.h), picked here by layout from
 // the instantiation units (rtla_kspec_*, rtla_ksym_*, rtla_kgeneric_*), or of
 // the wave-per-state fallback k_expand (rtla_kwave.hip).  This unit also
 // holds the multi-shard exchange kernels (k_insert_remote, and the level-end
 // re-balancing's k_stage_rows / k_unpack_rows), Init's insert, the synthetic microbench's state generator
 // and the fingerprint-set calibration kernel.
-#include "rtla_kernels_common.h"
+#include "rtla_klevel.h"
 
 using namespace rtla;
 
@@ -92,29 +92,8 @@ __global__ void k_requeue(const unsigned long long* __restrict__ in_fp, const un
       b = shfl_u64(b, __builtin_ctzll(m));
       if (o == p) slot = b + __popcll(m & lanes_below);
     }
-    if (act && slot < box.cap) {
-      const unsigned long long q = (unsigned long long)o * box.cap + slot;
-      box.send_fp[2 * q] = f.a;
-      box.send_fp[2 * q + 1] = f.b;
-      box.send_ref[q] = ref;
-    }
-    const bool ov = act && slot >= box.cap;
-    const unsigned long long om = __ballot(ov);
-    if (om) {
-      unsigned long long ob = 0;
-      if (lane == 0) ob = atomicAdd(box.over_count, (unsigned long long)__popcll(om));
-      ob = shfl0_u64(ob);
-      if (ov) {
-        const unsigned long long q = ob + __popcll(om & lanes_below);
-        if (q < box.over_cap) {
-          box.over_fp[2 * q] = f.a;
-          box.over_fp[2 * q + 1] = f.b;
-          box.over_ref[q] = ref;
-        } else {
-          set_flag(ctr, FLAG_OUTBOX_FULL);
-        }
-      }
-    }
+    if (act && slot < box.cap) outbox_put(box, o, slot, f, ref);
+    overflow_put(box, act && slot >= box.cap, f, ref, ctr, lane);
   }
 }
 
@@ -284,7 +263,7 @@ int expand_blocks_per_cu(const Layout& L) {
 
 // The instantiation of k_expand_compact for a's layout: the compiled-in
 // BASELINE layouts first, then the run-time layout.  *done = one took it.
-static hipError_t launch_compact_any(const CompactArgs& a, bool* done) {
+static hipError_t launch_compact_any(const LevelArgs& a, bool* done) {
   hipError_t e = hipSuccess;
   *done = false;
   if (!(a.xflags & XF_NO_SPECIAL)) {
@@ -300,30 +279,19 @@ static hipError_t launch_compact_any(const CompactArgs& a, bool* done) {
   return e;
 }
 
-hipError_t launch_expand(const Layout& L, const Ring& cur, uint64_t s_begin, uint64_t s_end, uint64_t cur_base,
-                         const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap, uint64_t* table,
-                         int tlog2, DevCounters* ctr, const ShardBox& box, int grid, hipStream_t st, int xflags,
-                         uint64_t* sent, hipEvent_t mid) {
-  if (s_end <= s_begin) return hipSuccess;
-  const int cwpb = expand_compact_wpb(L);
-  if (cwpb > 0 && !(xflags & XF_WAVE_KERNEL)) {
-    const CompactArgs a{L,         box.nshard > 1, cur,      s_begin, s_end,  cur_base, next,   parents, next_base,
-                        next_cap,  table,          tlog2,    ctr,     box,    st,       xflags, sent,
-                        (xflags & XF_BLOCK4) ? cwpb : 1};  // one-wave workgroups by default
-    bool done = false;
-    hipError_t e = launch_compact_any(a, &done);
-    if (!done) return hipErrorNotSupported;
+hipError_t launch_expand(const LevelArgs& a, hipEvent_t mid) {
+  if (a.s_end <= a.s_begin) return hipSuccess;
+  // one wave per state: rows too wide for the compacting kernel's LDS tile (or forced, XF_WAVE_KERNEL)
+  if (expand_compact_wpb(a.L) <= 0 || (a.xflags & XF_WAVE_KERNEL)) return launch_wave_expand(a);
+  bool done = false;
+  hipError_t e = launch_compact_any(a, &done);
+  if (!done) return hipErrorNotSupported;
+  if (e != hipSuccess) return e;
+  if (mid) {
+    e = hipEventRecord(mid, a.st);
     if (e != hipSuccess) return e;
-    if (mid) {
-      e = hipEventRecord(mid, st);
-      if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
   }
-  // one wave per state: rows too wide for the compacting kernel's LDS tile
-  // (or forced, XF_WAVE_KERNEL)
-  return launch_wave_expand(L, cur, s_begin, s_end, cur_base, next, parents, next_base, next_cap, table, tlog2, ctr,
-                            box, grid, st);
+  return hipGetLastError();
 }
 
 bool level_kernel_shape(const Layout& L, bool multi, int xflags, int* waves, int* group) {
@@ -331,13 +299,10 @@ bool level_kernel_shape(const Layout& L, bool multi, int xflags, int* waves, int
   *group = 0;
   if (expand_compact_wpb(L) <= 0 || (xflags & XF_WAVE_KERNEL)) return false;
   int q[2] = {0, 0};
-  CompactArgs a{};
+  LevelArgs a;
   a.L = L;
-  a.multi = multi;
-  a.s_begin = 0;
   a.s_end = 64;
   a.xflags = xflags;
-  a.wpb = (xflags & XF_BLOCK4) ? expand_compact_wpb(L) : 1;
   a.box.nshard = multi ? 2 : 1;
   a.query = q;
   bool done = false;
@@ -381,13 +346,13 @@ hipError_t launch_insert_remote(const uint64_t* recv_fp, const uint64_t* counts,
 }
 
 hipError_t launch_unpack_rows(int W, const uint32_t* rows, const uint64_t* counts, const uint64_t* bases, int nshard,
-                              uint64_t rows_cap, const Ring& next, uint64_t* parents, uint64_t next_base,
-                              uint64_t next_cap, DevCounters* ctr, uint64_t max_count, hipStream_t st) {
+                              uint64_t rows_cap, const FrontierOut& out, DevCounters* ctr, uint64_t max_count,
+                              hipStream_t st) {
   if (!max_count) return hipSuccess;
   hipLaunchKernelGGL(k_unpack_rows, dim3(grid_x(max_count, 4), nshard), dim3(256), 0, st, W, rows,
                      (const unsigned long long*)counts, (const unsigned long long*)bases, nshard,
-                     (unsigned long long)rows_cap, next, (unsigned long long*)parents, (unsigned long long)next_base,
-                     (unsigned long long)next_cap, ctr);
+                     (unsigned long long)rows_cap, out.next, (unsigned long long*)out.parents,
+                     (unsigned long long)out.next_base, (unsigned long long)out.next_cap, ctr);
   return hipGetLastError();
 }
 

@@ -1,9 +1,9 @@
 // rtla_kgeneric_a.hip -- level-kernel instantiations: any configuration with N = 1..3 on its run-time layout.
-#include "rtla_kernels_common.h"
+#include "rtla_klevel.h"
 
 namespace rtla {
 
-hipError_t launch_compact_generic_a(const CompactArgs& a, bool* done) {
+hipError_t launch_compact_generic_a(const LevelArgs& a, bool* done) {
   *done = true;
   const bool g64 = compact_group(a.L) == 64;
   switch (a.L.sym ? 0 : a.L.N) {

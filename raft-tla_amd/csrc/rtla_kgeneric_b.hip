@@ -1,9 +1,9 @@
 // rtla_kgeneric_b.hip -- level-kernel instantiations: any configuration with N = 4, 5 on its run-time layout.
-#include "rtla_kernels_common.h"
+#include "rtla_klevel.h"
 
 namespace rtla {
 
-hipError_t launch_compact_generic_b(const CompactArgs& a, bool* done) {
+hipError_t launch_compact_generic_b(const LevelArgs& a, bool* done) {
   *done = true;
   const bool g64 = compact_group(a.L) == 64;
   switch (a.L.sym ? 0 : a.L.N) {

@@ -1,251 +1,16 @@
-// rtla_kernels_common.h -- the level kernel (k_expand_compact) and the
-// device helpers every kernel translation unit shares.
+// rtla_klevel.h -- the level kernel k_expand_compact, its private helpers and
+// its launcher launch_compact (shared device helpers: rtla_kdev.h).
 //
 // The level kernel is a template over the server count, the group size, the
 // compiled-in layout and SYMMETRY; its instantiations are spread over several
-// translation units (rtla_kspec_*.hip, rtla_kgeneric_*.hip, rtla_ksym.hip)
-// that compile in parallel, each exporting one launcher
-// (launch_compact_*, rtla_launch.h); rtla_kernels.hip holds the other
-// kernels and the dispatch.
+// translation units (rtla_kspec_*.hip, rtla_ksym_*.hip, rtla_kgeneric_*.hip)
+// that compile in parallel, each exporting one launcher (launch_compact_*,
+// rtla_launch.h).  Only they and rtla_kernels.hip (the dispatch, the LDS
+// sizes) include this header.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdlib.h>
-
-#include <algorithm>
-
-#include "rtla_device.h"
-
-#include "rtla_model.h"
-#include "rtla_synth.h"
-#include "rtla_launch.h"
-
-using namespace rtla;
+#include "rtla_kdev.h"
 
 namespace {
-
-constexpr int STAGE_ROWS = 16;  // LDS staging rows per wave
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ unsigned long long shfl0_u64(unsigned long long v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return (unsigned long long)lo | (unsigned long long)hi << 32;
-}
-
-// Copy n contiguous words global -> LDS (dst and src 16-byte aligned) with 8
-// 16-byte loads in flight per lane (a plain loop waits for every load before
-// its LDS store).
-__device__ __forceinline__ void copy_words_lds16(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int n,
-                                                 int lane) {
-  const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
-  uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
-  const int n4 = n >> 2;
-  int w = lane;
-  for (; w + 7 * 64 < n4; w += 8 * 64) {
-    uint4 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = s4[w + j * 64];
-#pragma unroll
-    for (int j = 0; j < 8; j++) d4[w + j * 64] = v[j];
-  }
-  for (; w < n4; w += 64) d4[w] = s4[w];
-  for (int t = (n4 << 2) + lane; t < n; t += 64) dst[t] = src[t];
-}
-
-// Gather nv rows of W words (row r from src_row(r), a wave-uniform address)
-// into LDS rows dst + r * W: lane l moves words l, l + 64, ... of each row,
-// 8 rows (8 loads per lane) in flight.
-template <class F>
-__device__ __forceinline__ void gather_rows_lds(uint32_t* __restrict__ dst, int W, int nv, F src_row, int lane) {
-  for (int r0 = 0; r0 < nv; r0 += 8) {
-    for (int c = lane; c < W; c += 64) {
-      uint32_t v[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) v[j] = r0 + j < nv ? src_row(r0 + j)[c] : 0u;
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        if (r0 + j < nv) dst[(r0 + j) * W + c] = v[j];
-    }
-  }
-}
-
-// Row pointer of state g of a level (see Ring, rtla_device.h).
-__device__ __forceinline__ uint32_t* ring_row(const Ring& R, unsigned long long g, int W) {
-  return R.base + ring_idx(R, g) * (unsigned long long)W;
-}
-
-// Store nr consecutive rows (LDS src, W words each) as states g .. g + nr - 1
-// of the level R, coalesced; the range may wrap at the end of the arena.
-__device__ __forceinline__ void store_rows_ring(const Ring& R, unsigned long long g, int nr, int W,
-                                                const uint32_t* __restrict__ src, int lane) {
-  const unsigned long long p = ring_idx(R, g);
-  const int n1 = (int)min<unsigned long long>(R.cap - p, (unsigned long long)nr) * W;  // words before the wrap
-  uint32_t* d1 = R.base + p * (unsigned long long)W;
-  const int nw = nr * W;
-  for (int w = lane; w < nw; w += 64) {
-    if (w < n1) d1[w] = src[w];
-    else R.base[w - n1] = src[w];
-  }
-}
-
-// Insert into the fingerprint set.  1 = newly inserted, 0 = already present,
-// -1 = probe limit exceeded (set too full).  Slots only ever change 0 -> key;
-// the CAS both tests and claims a slot, so every probe is one round trip.
-__device__ __forceinline__ int fpset_insert(unsigned long long* table, int log2, FP f) {
-  const unsigned long long key = f.b | 1ull;
-  const unsigned long long mask = (1ull << log2) - 1ull;
-  unsigned long long idx = f.a >> (64 - log2);
-  for (int probe = 0; probe < 4096; probe++) {
-    unsigned long long old = atomicCAS(&table[idx], 0ull, key);
-    if (old == 0ull) return 1;
-    if (old == key) return 0;
-    idx = (idx + 1ull) & mask;
-  }
-  return -1;
-}
-
-__device__ __forceinline__ void set_flag(DevCounters* c, int f) { atomicOr(&c->flags, f); }
-
-// The first violation found wins and is never replaced.  Called by the whole
-// wave (bad = this lane's violated-invariant mask, 0 if none): one CAS per
-// wave -- its first violating lane -- and none once a violation has been
-// recorded, so successors that all violate an invariant (random states, or
-// a violation reached by many parents) do not serialise on that one word.
-// Returns true on the lane whose violation was recorded.
-__device__ __forceinline__ bool claim_violation(DevCounters* c, int bad, int lane) {
-  const unsigned long long m = __ballot(bad != 0);
-  if (!m) return false;
-  if (lane != __builtin_ctzll(m)) return false;
-  if (__hip_atomic_load(&c->viol_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-  return atomicCAS(&c->viol_mask, 0, bad) == 0;
-}
-
-// Finish an insert whose home slot `idx` was READ (not CAS'd) as `seen`.
-// Slots only ever change 0 -> key, so a slot holding the key proves the
-// state is present, and one holding another key can be skipped for good;
-// only an empty slot needs the CAS (which may then find the key after all).
-__device__ __forceinline__ bool fpset_resolve_loaded(unsigned long long* table, int log2, unsigned long long key,
-                                                     unsigned long long idx, unsigned long long seen,
-                                                     DevCounters* ctr) {
-  const unsigned long long mask = (1ull << log2) - 1ull;
-  for (int probe = 1;; probe++) {
-    if (seen == key) return false;
-    if (seen == 0ull) {
-      seen = atomicCAS(&table[idx], 0ull, key);
-      if (seen == 0ull) return true;
-      if (seen == key) return false;
-    }
-    if (probe >= 4096) {
-      set_flag(ctr, FLAG_FPSET_FULL);
-      return false;
-    }
-    idx = (idx + 1ull) & mask;
-    seen = __hip_atomic_load(&table[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// RTLA_CHECKED builds: every global row / parent-record index is checked
-// against the buffer capacities the host stores in DevCounters; a bad index
-// raises FLAG_BAD_INDEX (reported by rtla_step) instead of faulting.
-#ifdef RTLA_CHECKED
-#define RTLA_IDX_OK(ctr, idx, cap) ((idx) < (cap) ? true : (set_flag((ctr), FLAG_BAD_INDEX), false))
-#else
-#define RTLA_IDX_OK(ctr, idx, cap) true
-#endif
-
-// Finish an insert whose first CAS (at home slot `idx`) returned `old`:
-// continue linear probing while the slot holds another key.  true = new.
-__device__ __forceinline__ bool fpset_resolve(unsigned long long* table, int log2, unsigned long long key,
-                                              unsigned long long idx, unsigned long long old, DevCounters* ctr) {
-  const unsigned long long mask = (1ull << log2) - 1ull;
-  for (int probe = 1; old != 0ull && old != key; probe++) {
-    if (probe >= 4096) {
-      set_flag(ctr, FLAG_FPSET_FULL);
-      return false;
-    }
-    idx = (idx + 1ull) & mask;
-    old = atomicCAS(&table[idx], 0ull, key);
-  }
-  return old == 0ull;
-}
-
-// Map the q-th candidate of a parent with `nmsg` bag slots to an instance id:
-// the fixed families first, then Receive / Duplicate / Drop over used slots.
-__device__ __forceinline__ int candidate_inst(const Layout& L, int q, int nmsg) {
-  const int fixed = L.fam[F_RECEIVE];
-  if (q < fixed) return q;
-  int r = q - fixed;
-  int fam = r / nmsg, slot = r - fam * nmsg;
-  return fam_base(L, F_RECEIVE + fam) + slot;
-}
-
-__device__ __forceinline__ int inst_family(const Layout& L, int inst) {
-  int fam = 0;
-#pragma unroll
-  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
-  return fam;
-}
-
-__device__ __forceinline__ int cover_code(const Layout& L, int inst, int sub) {
-  const int fam = inst_family(L, inst);
-  return fam == F_RECEIVE ? F_COUNT + sub : fam;
-}
-
-// Per-wave LDS: parent row (W, padded to even) | new allLogs words (32) |
-// parent server-record hashes (NMAX FPs = 4 * NMAX words, 8-byte aligned) |
-// staging rows (STAGE_ROWS * W).  The per-wave block is a multiple of 4
-// words so every wave's hash slots stay 8-byte aligned.
-__host__ __device__ constexpr int even_words(int W) { return (W + 1) & ~1; }
-__host__ __device__ constexpr int wave_lds_words(int W) {
-  return (even_words(W) + 32 + 4 * NMAX + STAGE_ROWS * W + 3) & ~3;
-}
-
-// (the readlane builtins return a signed int: widen through uint32_t)
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-  return (unsigned long long)lo | (unsigned long long)hi << 32;
-}
-
-// SYMMETRY: the successor parent + d through sym_key's accessors (server
-// records, bag slots, election records), without materialising it:
-// f(rec_of, nmsg, slot_of, nelec, elec_of).
-template <int NS, class P, class F>
-__device__ __forceinline__ auto with_successor(const Layout& L, P prow, const DeltaT<NS>& d, F f) {
-  constexpr int EW = 2 + NS;
-  const int ne0 = row_nelec(L, prow);
-  auto rec_of = [&](int i, uint32_t* out) {
-    load_rec<NS>(L, prow, i, out);
-    if (i == d.srv) {
-#pragma unroll
-      for (int w = 0; w < 3 + NS; w++) out[w] = d.rec[w];
-    }
-  };
-  auto slot_of = [&](int q) { return bag_get(L, prow, d, q); };
-  auto elec_of = [&](int e, uint32_t* out) {
-    if (e < ne0) {
-      out[0] = elec_w0(L, prow, e);
-      out[1] = elec_log(L, prow, e);
-#pragma unroll
-      for (int j = 0; j < NS; j++) out[2 + j] = elec_vl(L, prow, e, j);
-    } else {
-#pragma unroll
-      for (int w = 0; w < EW; w++) out[w] = d.erec[w];
-    }
-  };
-  return f(rec_of, d.nmsg, slot_of, ne0 + (d.elec ? 1 : 0), elec_of);
-}
-// Orbit key of the successor parent + d (allLogs' fingerprint afp).
-template <int NS, class P>
-__device__ __forceinline__ FP successor_orbit_key(const Layout& L, P prow, const DeltaT<NS>& d, FP afp) {
-  return with_successor<NS>(L, prow, d, [&](auto rec_of, int nmsg, auto slot_of, int nelec, auto elec_of) {
-    return sym_key<NS>(L, rec_of, nmsg, slot_of, nelec, elec_of, afp);
-  });
-}
 
 // a[j] += v for a run-time j (selects)
 template <int NS>
@@ -303,54 +68,6 @@ __device__ __forceinline__ int successor_orbit_step_sig(const Layout& L, P prow,
     return k1 < r.ncomb ? k1 : -1;
   });
 }
-
-// Load the parent row into LDS and derive the per-parent data every lane
-// needs.  Returns the parent fingerprint with allLogs' already applied.
-template <int NS>
-__device__ __forceinline__ FP load_parent(const Layout& L, const uint32_t* __restrict__ src, uint32_t* prow,
-                                          uint32_t* pall, FP* hsrv, int lane) {
-  const int W = L.W;
-  for (int w = lane; w < W; w += 64) prow[w] = src[w];
-  wave_sync();
-  FP afp{0, 0};
-  if (lane < NS) {
-    uint32_t rec[3 + NS];
-    load_rec<NS>(L, prow, lane, rec);
-    hsrv[lane] = h_srv(lane, rec, 3 + NS);
-  } else if (lane == NS) {
-    afp = alllogs_delta<NS>(L, prow, pall);
-  }
-  afp.a = readlane_u64(afp.a, NS);
-  afp.b = readlane_u64(afp.b, NS);
-  wave_sync();
-  return fp_add(row_fp(prow), afp);
-}
-
-}  // namespace
-
-// Helpers of the lane-per-state phases (k_expand_compact, k_pack_rows).
-namespace {
-
-struct LaneWords {  // word w of a per-lane array kept word-major (stride 64: bank-conflict free)
-  uint32_t* p;
-  __device__ __forceinline__ uint32_t& operator[](int w) const { return p[w * 64]; }
-};
-template <int S>
-struct StridedWords {  // the same with stride S (one array per state of an S-state group)
-  uint32_t* p;
-  __device__ __forceinline__ uint32_t& operator[](int w) const { return p[w * S]; }
-};
-
-__device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
-  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo |= (uint32_t)__shfl_xor((int)lo, o);
-    hi |= (uint32_t)__shfl_xor((int)hi, o);
-  }
-  return (unsigned long long)lo | (unsigned long long)hi << 32;
-}
-__host__ __device__ constexpr int lane_lds_words(int W, int AW) { return 64 * W + 64 * AW; }
 
 }  // namespace
 
@@ -454,12 +171,6 @@ __device__ __forceinline__ unsigned long long home_slot(const FP& key, int lg) {
   return lg ? key.a >> (64 - lg) : 0ull;
 }
 
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src);
-  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return (unsigned long long)lo | (unsigned long long)hi << 32;
-}
-
 }  // namespace
 
 #ifndef RTLA_COMPACT_WAVES_PER_EU
@@ -469,14 +180,6 @@ __device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int
 #define RTLA_SYM_WAVES_PER_EU 4      // SYMMETRY, the key pass a call of its own (key_one): 128 VGPRs (configs[3]:
                                      // 311.5 ms, 16-state groups) beat 168 (343 ms) and 102 (414 ms)
 #endif
-// The layout the kernel runs on: the run-time argument, or (LC.N != 0) the
-// configuration compiled in as a template parameter, whose fields the
-// compiler then folds into every offset, bound and loop of the model code.
-template <Layout LC>
-__device__ __forceinline__ const Layout& pick_layout(const Layout& rt) {
-  if constexpr (LC.N == 0) return rt;
-  else return LC;
-}
 
 namespace {
 // One key_chunk lane as a function of its own: the successor's Delta, then
@@ -628,8 +331,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     }
     wave_sync();
   }
-  for (int k = threadIdx.x; k < 2 * COVER_CODES; k += blockDim.x) cov[k] = 0;
-  __syncthreads();
+  cover_zero(cov, 2 * COVER_CODES);
 
   unsigned my_gen = 0, my_probe = 0;
   unsigned my_dup = 0;  // DuplicateMessage successors counted, not evaluated (dup_counted)
@@ -751,6 +453,8 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   auto build_all = [&]() {
     const int ntot = tail - head;  // uniform
     if (ntot == 0) return;
+    // (reserve_rows and the record functions of rtla_device.h, spelled out: calling them here changes the
+    // kernel's register allocation -- spilled VGPRs of every instantiation, profiles/r08_kdev)
     unsigned long long obase = 0;
     if (lane == 0) obase = atomicAdd(&ctr->next_count, (unsigned long long)ntot);
     obase = shfl0_u64(obase);
@@ -790,12 +494,8 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
                                       rows_on && child < nrows, rows_on && b == 0);
         else if (rows_on && b == 0)
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (!(xflags & XF_ALL_SUCCESSORS) && claim_violation(ctr, o.bad, lane)) {
-          ctr->viol_parent = cur_base + s0 + sl;
-          ctr->viol_inst = inst;
-          ctr->viol_in_model = 1;
-          ctr->viol_child = child < nrows ? next_base + obase + child : ~0ull;
-        }
+        if (!(xflags & XF_ALL_SUCCESSORS) && claim_violation(ctr, o.bad, lane))
+          record_violation(ctr, cur_base + s0 + sl, inst, 1, child < nrows ? next_base + obase + child : ~0ull);
         cover_add(cov + COVER_CODES, act, inst, o.sub);  // distinct coverage
         if (child < nrows && RTLA_IDX_OK(ctr, next_base + obase + child, ctr->cap_parents))
           parents[next_base + obase + child] =
@@ -816,12 +516,8 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
         cfp = fp_add(qfp, delta_fp<NS>(L, prow, d));
         bad = check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
       }
-      if (!(xflags & XF_ALL_SUCCESSORS) && claim_violation(ctr, bad, lane)) {
-        ctr->viol_parent = cur_base + s0 + sl;
-        ctr->viol_inst = inst;
-        ctr->viol_in_model = 1;
-        ctr->viol_child = child < nrows ? next_base + obase + child : ~0ull;
-      }
+      if (!(xflags & XF_ALL_SUCCESSORS) && claim_violation(ctr, bad, lane))
+        record_violation(ctr, cur_base + s0 + sl, inst, 1, child < nrows ? next_base + obase + child : ~0ull);
       cover_add(cov + COVER_CODES, act, inst, d.sub);  // distinct coverage
       uint32_t spk[PACKW], epk[PACKW];  // the changed records, packed
       if (act) child_pack(L, d, spk, epk);
@@ -932,15 +628,11 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
         room = __shfl(room, src);
         const int r = __popcll(mym & lanes_below);
         const unsigned long long slot = r < room ? b1 + r : b2 + (r - room);
-        const unsigned long long ref = (s0 + (rinfo >> 16)) << 16 | (unsigned long long)(rinfo & 0xffffu);
-        if (rem && slot < box.cap) {
-          const unsigned long long k = (unsigned long long)powner * box.cap + slot;
-          box.send_fp[2 * k] = pf.a;
-          box.send_fp[2 * k + 1] = pf.b;
-          box.send_ref[k] = ref;
-        }
+        const unsigned long long ref = outbox_ref(s0 + (rinfo >> 16), rinfo & 0xffffu);
+        if (rem && slot < box.cap) outbox_put(box, powner, slot, pf, ref);
         // past the region's end (the groups in flight when it filled): the
-        // overflow list, sent next round
+        // overflow list, sent next round (overflow_put, rtla_kdev.h, spelled
+        // out: the call changes the N = 1 SYMMETRY kernel's register allocation)
         const bool ov = rem && slot >= box.cap;
         const unsigned long long om = __ballot(ov);
         if (om) {
@@ -988,11 +680,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     DeltaFpT<NS> d;
     d.enabled = 0;
     if (!(xflags & XF_NO_DELTA)) chunk_delta(active, prow, inst, d);
-    bool en = d.enabled != 0;
-    if (en && d.err) {
-      set_flag(ctr, d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW);
-      en = false;
-    }
+    const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
     my_gen += en ? 1u : 0u;
     bool kq = false;
     nprobe = false;
@@ -1029,12 +717,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     int bad = 0;
     if (en && !d.in_model && !(xflags & (XF_DEDUP_ONLY | XF_ALL_SUCCESSORS)))
       bad = check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
-    if (claim_violation(ctr, bad, lane)) {
-      ctr->viol_parent = cur_base + s0 + sl;
-      ctr->viol_inst = inst;
-      ctr->viol_in_model = 0;
-      ctr->viol_child = ~0ull;
-    }
+    if (claim_violation(ctr, bad, lane)) record_violation(ctr, cur_base + s0 + sl, inst, 0, ~0ull);
   };
   // SYMMETRY: orbit keys, one successor per lane: the ccount continuations
   // first, then kring[kd, kd + kc) -- the full Delta (the probe pass only
@@ -1330,25 +1013,10 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
 #endif
   STAMP(7);  // (kernel end: negligible)
   RTLA_STAMP_FLUSH(ctr, lane)
-  __syncthreads();
-  for (int k = threadIdx.x; k < 2 * COVER_CODES; k += blockDim.x)
-    if (cov[k]) atomicAdd(&ctr->cover[k], (unsigned long long)cov[k]);
+  cover_flush(cov, 2 * COVER_CODES, ctr->cover);
 }
 
 namespace rtla {
-
-#define RTLA_DISPATCH_N(L, KERNEL, ...)                        \
-  switch ((L).N) {                                             \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break; \
-    case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break; \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break; \
-  }
-
-static inline unsigned grid_x(uint64_t n, int per_block) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, 4096));
-}
 
 // States per wave-group of k_expand_compact: 64, or 32 when 64 rows would
 // make the per-wave LDS tile so large that fewer than ~11 waves fit a CU.
@@ -1377,41 +1045,12 @@ constexpr int spec_group(const Layout& L) {
   return g == 32 && compact_lds_words(L.W, L.all_words, 32, L.sym, true) * sizeof(uint32_t) > RTLA_GROUP32_LDS ? 16 : g;
 }
 
-static inline int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
-
-// Configurations whose layout is compiled into k_expand_compact (the BASELINE
-// workloads bench.py runs); any other configuration runs the same kernel on
-// its run-time layout.
-namespace specs {
-constexpr Layout CFG2 = layout_of(3, 2, 3, 2, 1, 0, 18, 6, INV_ELECTION_SAFETY | INV_LOG_MATCHING);  // configs[1]
-constexpr Layout CFG1 = layout_of(3, 1, 2, 1, 1, 0, 24, 3, INV_NO_TWO_LEADERS);                     // configs[0]
-constexpr Layout EXHAUST = layout_of(3, 2, 2, 2, 1, 2, 3, 3, INV_ELECTION_SAFETY | INV_LOG_MATCHING);
-constexpr Layout CFG3 = layout_of(3, 2, 4, 3, 2, 0, 20, 9, 0);                                      // configs[2]
-constexpr Layout SYNTH = layout_of(3, 2, 4, 3, 2, 0, 12, 9, INV_ELECTION_SAFETY | INV_LOG_MATCHING);  // configs[4]
-constexpr Layout symmetric(Layout l) {
-  l.sym = 1;
-  return l;
-}
-constexpr Layout CFG4 = symmetric(layout_of(5, 1, 3, 2, 1, 0, 20, 10, 0));  // configs[3], SYMMETRY
-static_assert(CFG2.N == 3 && CFG1.N == 3 && EXHAUST.N == 3 && CFG3.N == 3 && SYNTH.N == 3 && CFG4.N == 5,
-              "compiled-in layouts must be valid");
-}  // namespace specs
-
 template <int NS, int GROUP, Layout LC, bool SYM = false>
-static hipError_t launch_compact(const CompactArgs& a) {
+static hipError_t launch_compact(const LevelArgs& a) {
   const Layout& L = a.L;
-  const bool multi = a.multi;
-  const int wpb = a.wpb, xflags = a.xflags;
+  const bool multi = a.box.nshard > 1;
+  const int xflags = a.xflags;
+  const int wpb = (xflags & XF_BLOCK4) ? expand_compact_wpb(L) : 1;  // one-wave workgroups by default
   const uint64_t s_begin = a.s_begin, s_end = a.s_end;
   DevCounters* ctr = a.ctr;
   hipStream_t st = a.st;
@@ -1440,11 +1079,10 @@ static hipError_t launch_compact(const CompactArgs& a) {
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(64 * wpb), lds, st, L, a.cur, (unsigned long long)s_begin,
-                     (unsigned long long)s_end, (unsigned long long)a.cur_base, a.next,
-                     (unsigned long long*)a.parents, (unsigned long long)a.next_base, (unsigned long long)a.next_cap,
-                     (unsigned long long*)a.table, (unsigned long long*)a.sent, a.tlog2, ctr, a.box, xflags);
+                     (unsigned long long)s_end, (unsigned long long)a.cur_base, a.out.next,
+                     (unsigned long long*)a.out.parents, (unsigned long long)a.out.next_base,
+                     (unsigned long long)a.out.next_cap, (unsigned long long*)a.table, (unsigned long long*)a.sent, a.tlog2, ctr, a.box, xflags);
   return hipGetLastError();
 }
-
 
 }  // namespace rtla

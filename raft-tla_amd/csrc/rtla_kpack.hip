@@ -1,7 +1,8 @@
 // rtla_kpack.hip -- lane-per-state row builders: the multi-shard sender's
 // k_build_winners and the wave-per-state k_expand_batch (the parity seam's
-// fallback for rows too wide for the level kernel).
-#include "rtla_kernels_common.h"
+// fallback for rows too wide for the level kernel).  Shared device helpers,
+// pick_layout and the compiled-in layouts: rtla_kdev.h.
+#include "rtla_kdev.h"
 
 // Sender side of the two-phase exchange: the owners
 // answered every queued (fingerprint, parent) record with "new" (nonzero) or
@@ -44,11 +45,10 @@ k_build_winners(Layout Lrt, Ring cur, unsigned long long cur_base, int me,
   uint32_t* lrows = lds + wave * build_winners_lds_words(W, AW);
   const LaneWords pall{lrows + 64 * W + lane};
   unsigned long long* q = reinterpret_cast<unsigned long long*>(lrows + lane_lds_words(W, AW));
-  for (int k = threadIdx.x; k < COVER_CODES; k += blockDim.x) cov[k] = 0;
-  __syncthreads();
+  cover_zero(cov, COVER_CODES);
   const unsigned long long p = blockIdx.y;  // owner shard
   const unsigned long long n = min(counts[p], cap);  // (reservations may run past the region: the overflow list)
-  // build the first nw queued winners (q[0, nw): parent index << 16 | instance)
+  // build the first nw queued winners (q[0, nw): their outbox refs)
   auto build = [&](int nw) {
     // export slots for all nw (owner p's region), or none: the batch then goes
     // to this shard's next level.  One atomicAdd (a CAS loop that reserves only
@@ -66,15 +66,11 @@ k_build_winners(Layout Lrt, Ring cur, unsigned long long cur_base, int me,
     ebase = shfl0_u64(ebase);
     const bool exported = ebase != ~0ull;
     unsigned long long obase = 0;
-    if (!exported) {
-      if (lane == 0) obase = atomicAdd(&ctr->next_count, (unsigned long long)nw);
-      obase = shfl0_u64(obase);
-      if (obase + nw > next_cap && lane == 0) set_flag(ctr, FLAG_FRONTIER_FULL);
-    }
+    if (!exported) obase = reserve_rows(&ctr->next_count, nw, next_cap, ctr, lane);
     const bool act = lane < nw;
     const unsigned long long ref = act ? q[lane] : 0ull;
-    const unsigned long long s = ref >> 16;  // parent: state s of the current level
-    const int inst = (int)(ref & 0xffffull);
+    const unsigned long long s = outbox_parent(ref);  // parent: state s of the current level
+    const int inst = outbox_inst(ref);
     gather_rows_lds(lrows, W, nw, [&](int r) { return ring_row(cur, readlane_u64(s, r), W); }, lane);
     wave_sync();
     uint32_t* prow = lrows + lane * W;
@@ -84,19 +80,14 @@ k_build_winners(Layout Lrt, Ring cur, unsigned long long cur_base, int me,
       compute_delta<NS>(L, prow, inst, d);
       const FP cfp = fp_add(pfp, delta_fp<NS>(L, prow, d));
       const int bad = check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
-      if (bad && __hip_atomic_load(&ctr->viol_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 &&
-          atomicCAS(&ctr->viol_mask, 0, bad) == 0) {
-        ctr->viol_parent = cur_base + s;
-        ctr->viol_inst = inst;
-        ctr->viol_in_model = 1;
-        // (an exported row has no home yet: the trace replays the instance from the parent)
-        ctr->viol_child = !exported && obase + lane < next_cap ? next_base + obase + lane : ~0ull;
-      }
+      if (claim_violation_lane(ctr, bad))  // (an exported row has no home yet: the trace replays the instance from the parent)
+        record_violation(ctr, cur_base + s, inst, 1,
+                         !exported && obase + lane < next_cap ? next_base + obase + lane : ~0ull);
       atomicAdd(&cov[cover_code(L, inst, d.sub)], 1u);
       materialize<NS>(L, prow, d, pall, cfp, prow);  // in place
     }
     wave_sync();
-    const unsigned long long prec = (unsigned long long)me << 56 | (cur_base + s) << 16 | (unsigned long long)inst;
+    const unsigned long long prec = parent_record(me, cur_base + s, inst);
     if (exported) {  // the k_unpack_rows format: W row words, then the parent record's two halves
       const int RW = W + 2;
       uint32_t* dst = exp_rows + ((unsigned long long)p * exp_cap + ebase) * (unsigned long long)RW;
@@ -136,13 +127,11 @@ k_build_winners(Layout Lrt, Ring cur, unsigned long long cur_base, int me,
     }
   }
   if (qn) build(qn);
-  __syncthreads();
-  for (int k = threadIdx.x; k < COVER_CODES; k += blockDim.x)
-    if (cov[k]) atomicAdd(&ctr->cover[COVER_CODES + k], (unsigned long long)cov[k]);
+  cover_flush(cov, COVER_CODES, ctr->cover + COVER_CODES);  // distinct coverage
 }
 
 // Parity seam: every enabled successor of every input row (in-model or not),
-// materialised.  out_info[k] = input index << 32 | in_model << 31 | sub << 16 | inst.
+// materialised.  out_info[k] = the successor record (successor_info, rtla_device.h).
 template <int NS>
 __global__ void __launch_bounds__(256)
 k_expand_batch(Layout L, const uint32_t* __restrict__ rows, unsigned long long n, uint32_t* __restrict__ out,
@@ -151,10 +140,7 @@ k_expand_batch(Layout L, const uint32_t* __restrict__ rows, unsigned long long n
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   const int W = L.W;
-  uint32_t* prow = lds + wave * wave_lds_words(W);
-  uint32_t* pall = prow + even_words(W);
-  FP* hsrv = reinterpret_cast<FP*>(pall + 32);
-  uint32_t* stage = pall + 32 + 4 * NMAX;
+  const auto [prow, pall, hsrv, stage] = wave_lds(lds, wave, W);
   const int fixed = L.fam[F_RECEIVE];
   for (unsigned long long s = (unsigned long long)blockIdx.x * wpb + wave; s < n;
        s += (unsigned long long)gridDim.x * wpb) {
@@ -170,22 +156,13 @@ k_expand_batch(Layout L, const uint32_t* __restrict__ rows, unsigned long long n
         inst = candidate_inst(L, q, nmsg);
         compute_delta<NS>(L, prow, inst, d);
       }
-      bool en = d.enabled != 0;
-      if (en && d.err) {
-        set_flag(ctr, d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW);
-        en = false;
-      }
+      const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
       const unsigned long long m = __ballot(en);
       const int cnt = __popcll(m);
       if (!cnt) continue;
       const int rank = __popcll(m & ((1ull << lane) - 1ull));
-      unsigned long long obase = 0;
-      if (lane == 0) obase = atomicAdd(&ctr->next_count, (unsigned long long)cnt);
-      obase = shfl0_u64(obase);
-      if (obase + cnt > cap) {
-        if (lane == 0) set_flag(ctr, FLAG_FRONTIER_FULL);
-        continue;
-      }
+      const unsigned long long obase = reserve_rows(&ctr->next_count, cnt, cap, ctr, lane);
+      if (obase + cnt > cap) continue;  // (a batch that does not fit whole is dropped)
       const FP cfp = en ? fp_add(pfp, delta_fp<NS>(L, prow, d)) : FP{0, 0};
       for (int b = 0; b < cnt; b += STAGE_ROWS) {
         if (en && rank >= b && rank < b + STAGE_ROWS) materialize<NS>(L, prow, d, pall, cfp, stage + (rank - b) * W);
@@ -195,58 +172,37 @@ k_expand_batch(Layout L, const uint32_t* __restrict__ rows, unsigned long long n
         for (int w = lane; w < nb * W; w += 64) dst[w] = stage[w];
         wave_sync();
       }
-      if (en)
-        out_info[obase + rank] = s << 32 | (unsigned long long)(d.in_model ? 1u : 0u) << 31 |
-                                 (unsigned long long)d.sub << 16 | (unsigned long long)inst;
+      if (en) out_info[obase + rank] = successor_info(s, d.in_model, d.sub, inst);
     }
   }
 }
 
 namespace rtla {
 
-template <int NS, Layout LC>
-static hipError_t build_winners(const Layout& L, const Ring& cur, uint64_t cur_base, int me, const uint64_t* send_ref,
-                                const uint32_t* ans, const uint64_t* counts, int nshard, uint64_t cap, const Ring& next,
-                                uint64_t* parents, uint64_t next_base, uint64_t next_cap, DevCounters* ctr,
-                                uint64_t max_count, uint32_t* exp_rows, uint64_t exp_cap, hipStream_t st) {
-  const size_t per = (size_t)build_winners_lds_words(L.W, L.all_words) * sizeof(uint32_t);
-  const int wpb = per * 4 <= 64 * 1024 ? 4 : (per * 2 <= 64 * 1024 ? 2 : 1);
-  const size_t lds = (size_t)wpb * per;
-  hipLaunchKernelGGL((k_build_winners<NS, LC>), dim3(grid_x(max_count, 1024 * wpb), nshard), dim3(64 * wpb), lds, st,
-                     L, cur, (unsigned long long)cur_base, me, (const unsigned long long*)send_ref, ans,
-                     (const unsigned long long*)counts, nshard, (unsigned long long)cap, next,
-                     (unsigned long long*)parents, (unsigned long long)next_base, (unsigned long long)next_cap, ctr,
-                     exp_rows, (unsigned long long)exp_cap);
-  return hipGetLastError();
-}
-
-hipError_t launch_build_winners(const Layout& L, const Ring& cur, uint64_t cur_base, int me, const uint64_t* send_ref,
-                                const uint32_t* ans, const uint64_t* counts, int nshard, uint64_t cap,
-                                const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap,
-                                DevCounters* ctr, uint64_t max_count, uint32_t* exp_rows, uint64_t exp_cap,
-                                hipStream_t st) {
-  if (!max_count) return hipSuccess;
-#define RTLA_BW(LC) \
-  return build_winners<LC.N, LC>(L, cur, cur_base, me, send_ref, ans, counts, nshard, cap, next, parents, next_base, \
-                                 next_cap, ctr, max_count, exp_rows, exp_cap, st)
+hipError_t launch_build_winners(const WinnerArgs& a) {
+  if (!a.max_count) return hipSuccess;
+  auto launch = [&](auto kernel) {
+    const size_t per = (size_t)build_winners_lds_words(a.L.W, a.L.all_words) * sizeof(uint32_t);
+    const int wpb = per * 4 <= 64 * 1024 ? 4 : (per * 2 <= 64 * 1024 ? 2 : 1);
+    hipLaunchKernelGGL(kernel, dim3(grid_x(a.max_count, 1024 * wpb), a.nshard), dim3(64 * wpb), (size_t)wpb * per,
+                       a.st, a.L, a.cur, (unsigned long long)a.cur_base, a.me, (const unsigned long long*)a.send_ref,
+                       a.ans, (const unsigned long long*)a.counts, a.nshard, (unsigned long long)a.cap, a.out.next,
+                       (unsigned long long*)a.out.parents, (unsigned long long)a.out.next_base,
+                       (unsigned long long)a.out.next_cap, a.ctr, a.exp_rows, (unsigned long long)a.exp_cap);
+    return hipGetLastError();
+  };
   // the BASELINE layouts bench.py shards (compiled in, as for the level kernel)
-  if (same_layout(L, specs::CFG2)) RTLA_BW(specs::CFG2);
-  if (same_layout(L, specs::CFG1)) RTLA_BW(specs::CFG1);
-  if (same_layout(L, specs::EXHAUST)) RTLA_BW(specs::EXHAUST);
-  if (same_layout(L, specs::CFG3)) RTLA_BW(specs::CFG3);
-  if (same_layout(L, specs::CFG4)) RTLA_BW(specs::CFG4);
-#undef RTLA_BW
-  switch (L.N) {
-    case 1: return build_winners<1, Layout{}>(L, cur, cur_base, me, send_ref, ans, counts, nshard, cap, next, parents,
-                                              next_base, next_cap, ctr, max_count, exp_rows, exp_cap, st);
-    case 2: return build_winners<2, Layout{}>(L, cur, cur_base, me, send_ref, ans, counts, nshard, cap, next, parents,
-                                              next_base, next_cap, ctr, max_count, exp_rows, exp_cap, st);
-    case 3: return build_winners<3, Layout{}>(L, cur, cur_base, me, send_ref, ans, counts, nshard, cap, next, parents,
-                                              next_base, next_cap, ctr, max_count, exp_rows, exp_cap, st);
-    case 4: return build_winners<4, Layout{}>(L, cur, cur_base, me, send_ref, ans, counts, nshard, cap, next, parents,
-                                              next_base, next_cap, ctr, max_count, exp_rows, exp_cap, st);
-    default: return build_winners<5, Layout{}>(L, cur, cur_base, me, send_ref, ans, counts, nshard, cap, next, parents,
-                                               next_base, next_cap, ctr, max_count, exp_rows, exp_cap, st);
+  if (same_layout(a.L, specs::CFG2)) return launch(k_build_winners<specs::CFG2.N, specs::CFG2>);
+  if (same_layout(a.L, specs::CFG1)) return launch(k_build_winners<specs::CFG1.N, specs::CFG1>);
+  if (same_layout(a.L, specs::EXHAUST)) return launch(k_build_winners<specs::EXHAUST.N, specs::EXHAUST>);
+  if (same_layout(a.L, specs::CFG3)) return launch(k_build_winners<specs::CFG3.N, specs::CFG3>);
+  if (same_layout(a.L, specs::CFG4)) return launch(k_build_winners<specs::CFG4.N, specs::CFG4>);
+  switch (a.L.N) {
+    case 1: return launch(k_build_winners<1, Layout{}>);
+    case 2: return launch(k_build_winners<2, Layout{}>);
+    case 3: return launch(k_build_winners<3, Layout{}>);
+    case 4: return launch(k_build_winners<4, Layout{}>);
+    default: return launch(k_build_winners<5, Layout{}>);
   }
 }
 

@@ -1,7 +1,8 @@
 // rtla_ksim.hip -- k_simulate: random walks from the current frontier (TLC's
 // -simulate; semantics in rtla_sim.h, the host replay computes the same walks).
 //   * one wavefront per walk, two row buffers in LDS (current and next state)
-//     plus the per-parent allLogs' words and server-record hashes;
+//     plus the per-parent allLogs' words and server-record hashes
+//     (parent_setup, rtla_kdev.h, as k_expand's load_parent);
 //   * each step the 64 lanes evaluate the state's action instances 64 at a
 //     time (k_expand's chunks); every enabled successor is counted and
 //     invariant-checked; lane c keeps the ballot of chunk c's in-model
@@ -11,7 +12,7 @@
 //     it (child_patches, incremental fingerprint: as materialize does);
 //   * global traffic: the start row, the end record, the counters -- and the
 //     current row of a walk whose depth is split across launches.
-#include "rtla_kernels_common.h"
+#include "rtla_kdev.h"
 #include "rtla_sim.h"
 
 namespace {
@@ -47,8 +48,7 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
   uint32_t* const wbase = lds + wave * sim_wave_words(W);
   uint32_t* const pall = wbase + 2 * even_words(W);
   FP* const hsrv = reinterpret_cast<FP*>(pall + 32);
-  for (int k = threadIdx.x; k < COVER_CODES; k += blockDim.x) taken[k] = 0;
-  __syncthreads();
+  cover_zero(taken, COVER_CODES);
 
   unsigned long long my_steps = 0, my_gen = 0, my_stuck = 0;  // wave-uniform
   const int fixed = L.fam[F_RECEIVE];
@@ -72,18 +72,7 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
     int len = t0, stop = SIM_STOP_DEPTH;
     for (int t = t0 + 1; t <= t1; t++) {
       // per-parent data: server-record hashes, allLogs' (raft.tla:465) and its fingerprint change
-      FP afp{0, 0};
-      if (lane < NS) {
-        uint32_t rec[3 + NS];
-        load_rec<NS>(L, a, lane, rec);
-        hsrv[lane] = h_srv(lane, rec, 3 + NS);
-      } else if (lane == NS) {
-        afp = alllogs_delta<NS>(L, a, pall);
-      }
-      afp.a = readlane_u64(afp.a, NS);
-      afp.b = readlane_u64(afp.b, NS);
-      wave_sync();
-      const FP pfp = fp_add(row_fp(a), afp);
+      const FP pfp = parent_setup<NS>(L, a, pall, hsrv, lane);
       const int nmsg = row_nmsg(L, a);
       const int ncand = min(fixed + 3 * nmsg, SIM_MAX_CAND);  // (the host refuses layouts with more)
       unsigned long long my_mask = 0;  // lane c: ballot of chunk c's in-model successors
@@ -100,11 +89,7 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
           inst = candidate_inst(L, q, nmsg);
           compute_delta<NS>(L, a, inst, d);
         }
-        bool en = d.enabled != 0;
-        if (en && d.err) {
-          atomicOr(&ctr->flags, d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW);
-          en = false;
-        }
+        const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
         my_gen += __popcll(__ballot(en));
         const int bad = en ? check_invariants_v<NS>(L, a, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]) : 0;
         const unsigned long long mb = __ballot(bad != 0);
@@ -181,9 +166,7 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
     if (my_gen) atomicAdd(&ctr->generated, my_gen);
     if (my_stuck) atomicAdd(&ctr->stuck, my_stuck);
   }
-  __syncthreads();
-  for (int k = threadIdx.x; k < COVER_CODES; k += blockDim.x)
-    if (taken[k]) atomicAdd(&ctr->taken[k], (unsigned long long)taken[k]);
+  cover_flush(taken, COVER_CODES, ctr->taken);
 }
 
 namespace rtla {

@@ -1,9 +1,9 @@
 // rtla_kspec_b.hip -- level-kernel instantiations: the compiled-in layouts of BASELINE configs[2], configs[4] and configs[3] (SYMMETRY).
-#include "rtla_kernels_common.h"
+#include "rtla_klevel.h"
 
 namespace rtla {
 
-hipError_t launch_compact_spec_b(const CompactArgs& a, bool* done) {
+hipError_t launch_compact_spec_b(const LevelArgs& a, bool* done) {
   *done = true;
   if (same_layout(a.L, specs::CFG3))
     return launch_compact<specs::CFG3.N, spec_group(specs::CFG3), specs::CFG3, (bool)specs::CFG3.sym>(a);

@@ -1,9 +1,9 @@
 // rtla_ksym_a.hip -- level-kernel instantiations: SYMMETRY on the run-time layout, N = 1..3 (32-state groups).
-#include "rtla_kernels_common.h"
+#include "rtla_klevel.h"
 
 namespace rtla {
 
-hipError_t launch_compact_sym_a(const CompactArgs& a, bool* done) {
+hipError_t launch_compact_sym_a(const LevelArgs& a, bool* done) {
   *done = true;
   if (!a.L.sym) {
     *done = false;

@@ -1,9 +1,9 @@
 // rtla_ksym_b.hip -- level-kernel instantiations: SYMMETRY on the run-time layout, N = 4, 5 (32-state groups).
-#include "rtla_kernels_common.h"
+#include "rtla_klevel.h"
 
 namespace rtla {
 
-hipError_t launch_compact_sym_b(const CompactArgs& a, bool* done) {
+hipError_t launch_compact_sym_b(const LevelArgs& a, bool* done) {
   *done = true;
   if (!a.L.sym) {
     *done = false;

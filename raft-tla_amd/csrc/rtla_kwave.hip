@@ -10,7 +10,8 @@
 //   * new successors are compacted by ballot + popcount prefix, built in a
 //     16-row LDS staging tile and written to the next frontier coalesced;
 //   * invariants are checked on every new and every out-of-model successor.
-#include "rtla_kernels_common.h"
+// (The helpers it shares with the other kernels: rtla_kdev.h.)
+#include "rtla_kdev.h"
 
 template <int NS>
 __global__ void __launch_bounds__(256)
@@ -23,12 +24,8 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   const int W = L.W;
-  uint32_t* prow = lds + wave * wave_lds_words(W);
-  uint32_t* pall = prow + even_words(W);
-  FP* hsrv = reinterpret_cast<FP*>(pall + 32);
-  uint32_t* stage = pall + 32 + 4 * NMAX;
-  for (int k = threadIdx.x; k < 2 * COVER_CODES; k += blockDim.x) cov[k] = 0;
-  __syncthreads();
+  const auto [prow, pall, hsrv, stage] = wave_lds(lds, wave, W);
+  cover_zero(cov, 2 * COVER_CODES);
 
   unsigned long long my_gen = 0, my_probe = 0;
   const int fixed = L.fam[F_RECEIVE];
@@ -48,11 +45,7 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
         inst = candidate_inst(L, q, nmsg);
         compute_delta<NS>(L, prow, inst, d);
       }
-      bool en = d.enabled != 0;
-      if (en && d.err) {
-        set_flag(ctr, d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW);
-        en = false;
-      }
+      const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
       my_gen += en ? 1 : 0;
       bool isnew = false;
       FP cfp{0, 0};
@@ -71,14 +64,8 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
           // Another shard owns this fingerprint: queue (fp, parent, instance);
           // the owner answers new/seen and this shard ships it the winner.
           unsigned long long slot = atomicAdd(&box.out_count[owner], 1ull);
-          if (slot < box.cap) {
-            unsigned long long k = (unsigned long long)owner * box.cap + slot;
-            box.send_fp[2 * k] = key.a;
-            box.send_fp[2 * k + 1] = key.b;
-            box.send_ref[k] = s << 16 | (unsigned long long)inst;
-          } else {
-            set_flag(ctr, FLAG_OUTBOX_FULL);
-          }
+          if (slot < box.cap) outbox_put(box, owner, slot, key, outbox_ref(s, inst));
+          else set_flag(ctr, FLAG_OUTBOX_FULL);
         }
       }
       if (en) {
@@ -92,11 +79,8 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
       int rank = 0;
       if (cnt) {
         rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) obase = atomicAdd(&ctr->next_count, (unsigned long long)cnt);
-        obase = shfl0_u64(obase);
-        if (obase + cnt > next_cap) {
-          if (lane == 0) set_flag(ctr, FLAG_FRONTIER_FULL);
-        } else {
+        obase = reserve_rows(&ctr->next_count, cnt, next_cap, ctr, lane);
+        if (obase + cnt <= next_cap) {  // (a batch that does not fit whole is dropped)
           // stage and write out STAGE_ROWS new rows at a time
           for (int b = 0; b < cnt; b += STAGE_ROWS) {
             if (isnew && rank >= b && rank < b + STAGE_ROWS)
@@ -105,20 +89,13 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
             store_rows_ring(next, obase + b, min(STAGE_ROWS, cnt - b), W, stage, lane);
             wave_sync();
           }
-          if (isnew)
-            parents[next_base + obase + rank] =
-                (unsigned long long)box.me << 56 | (cur_base + s) << 16 | (unsigned long long)inst;
+          if (isnew) parents[next_base + obase + rank] = parent_record(box.me, cur_base + s, inst);
         }
       }
       if (en && (isnew || !d.in_model)) {
-        int bad = check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
-        if (bad && __hip_atomic_load(&ctr->viol_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 &&
-            atomicCAS(&ctr->viol_mask, 0, bad) == 0) {
-          ctr->viol_parent = cur_base + s;
-          ctr->viol_inst = inst;
-          ctr->viol_in_model = d.in_model;
-          ctr->viol_child = isnew ? next_base + obase + rank : ~0ull;
-        }
+        const int bad = check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
+        if (claim_violation_lane(ctr, bad))
+          record_violation(ctr, cur_base + s, inst, d.in_model, isnew ? next_base + obase + rank : ~0ull);
       }
     }
   }
@@ -128,21 +105,16 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
   }
   if (lane == 0 && my_gen) atomicAdd(&ctr->generated, my_gen);
   if (lane == 0 && my_probe) atomicAdd(&ctr->probes, my_probe);
-  __syncthreads();
-  for (int k = threadIdx.x; k < 2 * COVER_CODES; k += blockDim.x)
-    if (cov[k]) atomicAdd(&ctr->cover[k], (unsigned long long)cov[k]);
+  cover_flush(cov, 2 * COVER_CODES, ctr->cover);
 }
 
 namespace rtla {
 
-hipError_t launch_wave_expand(const Layout& L, const Ring& cur, uint64_t s_begin, uint64_t s_end, uint64_t cur_base,
-                              const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap,
-                              uint64_t* table, int tlog2, DevCounters* ctr, const ShardBox& box, int grid,
-                              hipStream_t st) {
-  RTLA_DISPATCH_N(L, k_expand, dim3(grid), dim3(256), expand_lds_bytes(L, 4), st, L, cur,
-                  (unsigned long long)s_begin, (unsigned long long)s_end, (unsigned long long)cur_base, next,
-                  (unsigned long long*)parents, (unsigned long long)next_base, (unsigned long long)next_cap,
-                  (unsigned long long*)table, tlog2, ctr, box);
+hipError_t launch_wave_expand(const LevelArgs& a) {
+  RTLA_DISPATCH_N(a.L, k_expand, dim3(a.grid), dim3(256), expand_lds_bytes(a.L, 4), a.st, a.L, a.cur,
+                  (unsigned long long)a.s_begin, (unsigned long long)a.s_end, (unsigned long long)a.cur_base,
+                  a.out.next, (unsigned long long*)a.out.parents, (unsigned long long)a.out.next_base,
+                  (unsigned long long)a.out.next_cap, (unsigned long long*)a.table, a.tlog2, a.ctr, a.box);
   return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// rtla_launch.h -- host-side launch wrappers for the kernels in rtla_kernels.hip.
+// rtla_launch.h -- host-side launch wrappers for the kernels (csrc/*.hip) and their argument structs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,24 +16,30 @@ int expand_compact_wpb(const Layout& L);
 // Blocks of 4 waves that fit on one CU given the LDS footprint.
 int expand_blocks_per_cu(const Layout& L);
 
-// Arguments of one level-kernel launch (k_expand_compact).
-struct CompactArgs {
-  Layout L;
-  bool multi;
-  Ring cur;
-  uint64_t s_begin, s_end, cur_base;
+// Where a shard's new states of a level go: its next level's rows, the parent
+// records (record next_base + g for state g) and how many states fit.
+struct FrontierOut {
   Ring next;
   uint64_t* parents;
   uint64_t next_base, next_cap;
-  uint64_t* table;
-  int tlog2;
-  DevCounters* ctr;
-  ShardBox box;
-  hipStream_t st;
-  int xflags;
-  uint64_t* sent;
-  int wpb;
-  int* query = nullptr;  // non-null: store {waves launched at most, GROUP} of this launch, launch nothing
+};
+
+// Arguments of one level launch (launch_expand): frontier states [s_begin,
+// s_end) of `cur`, whose parent records start at cur_base.
+struct LevelArgs {
+  Layout L{};
+  Ring cur{};
+  uint64_t s_begin = 0, s_end = 0, cur_base = 0;
+  FrontierOut out{};
+  uint64_t* table = nullptr;
+  int tlog2 = 1;
+  DevCounters* ctr = nullptr;
+  ShardBox box{1, 0, 0, 0, nullptr, nullptr, nullptr};  // (one shard: no outbox)
+  hipStream_t st = nullptr;
+  int xflags = 0;
+  uint64_t* sent = nullptr;  // multi-shard: the sent cache
+  int grid = 1;              // blocks of the wave-per-state kernel
+  int* query = nullptr;      // non-null: store {waves launched at most, GROUP} of this launch, launch nothing
 };
 // The level kernel's shape for layout L (multi-shard or not): the most waves
 // one launch keeps resident and its frontier states per group.  false: the
@@ -54,23 +60,18 @@ hipError_t launch_round_tail(const DevCounters* ctr, uint64_t* out, int G, uint6
                              const uint64_t* over_count, hipStream_t st);
 // The level kernel's instantiations, one translation unit each (compiled in
 // parallel): *done = false if the unit has no kernel for a.L.
-hipError_t launch_compact_spec_a(const CompactArgs& a, bool* done);     // configs[1], configs[0], exhaust
-hipError_t launch_compact_spec_b(const CompactArgs& a, bool* done);     // configs[2], configs[4], configs[3] (SYMMETRY)
-hipError_t launch_compact_sym_a(const CompactArgs& a, bool* done);      // SYMMETRY, N = 1..3, run-time layout
-hipError_t launch_compact_sym_b(const CompactArgs& a, bool* done);      // SYMMETRY, N = 4, 5, run-time layout
-hipError_t launch_compact_generic_a(const CompactArgs& a, bool* done);  // N = 1..3, run-time layout
-hipError_t launch_compact_generic_b(const CompactArgs& a, bool* done);  // N = 4, 5, run-time layout
+hipError_t launch_compact_spec_a(const LevelArgs& a, bool* done);     // configs[1], configs[0], exhaust
+hipError_t launch_compact_spec_b(const LevelArgs& a, bool* done);     // configs[2], configs[4], configs[3] (SYMMETRY)
+hipError_t launch_compact_sym_a(const LevelArgs& a, bool* done);      // SYMMETRY, N = 1..3, run-time layout
+hipError_t launch_compact_sym_b(const LevelArgs& a, bool* done);      // SYMMETRY, N = 4, 5, run-time layout
+hipError_t launch_compact_generic_a(const LevelArgs& a, bool* done);  // N = 1..3, run-time layout
+hipError_t launch_compact_generic_b(const LevelArgs& a, bool* done);  // N = 4, 5, run-time layout
 
-hipError_t launch_expand(const Layout& L, const Ring& cur, uint64_t s_begin, uint64_t s_end,
-                         uint64_t cur_base, const Ring& next, uint64_t* parents, uint64_t next_base,
-                         uint64_t next_cap, uint64_t* table, int tlog2, DevCounters* ctr, const ShardBox& box,
-                         int grid, hipStream_t st, int xflags = 0, uint64_t* sent = nullptr,
-                         hipEvent_t mid = nullptr);  // recorded after the level kernel
+// One level (or exchange round) of one shard: k_expand_compact, or the wave-per-state k_expand for rows too wide
+// for its LDS tile (and XF_WAVE_KERNEL).  mid: recorded after the level kernel.
+hipError_t launch_expand(const LevelArgs& a, hipEvent_t mid = nullptr);
 // The wave-per-state level kernel (rtla_kwave.hip).
-hipError_t launch_wave_expand(const Layout& L, const Ring& cur, uint64_t s_begin, uint64_t s_end, uint64_t cur_base,
-                              const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap,
-                              uint64_t* table, int tlog2, DevCounters* ctr, const ShardBox& box, int grid,
-                              hipStream_t st);
+hipError_t launch_wave_expand(const LevelArgs& a);
 // Random walks from the frontier (rtla_ksim.hip, rtla_sim.h): walks [0, n_walks) of the batch starting at global
 // walk id `first`, steps t0 + 1 .. t1 of depth; carry (n_walks rows) only when the depth is split across launches.
 struct SimCounters;
@@ -81,14 +82,30 @@ hipError_t launch_simulate(const Layout& L, const Ring& cur, uint64_t n_front, u
 hipError_t launch_insert_remote(const uint64_t* recv_fp, const uint64_t* counts, int nshard, uint64_t cap,
                                 uint64_t* table, int tlog2, uint32_t* ans, DevCounters* ctr, uint64_t max_count,
                                 hipStream_t st);
-hipError_t launch_build_winners(const Layout& L, const Ring& cur, uint64_t cur_base, int me, const uint64_t* send_ref,
-                                const uint32_t* ans, const uint64_t* counts, int nshard, uint64_t cap,
-                                const Ring& next, uint64_t* parents, uint64_t next_base, uint64_t next_cap,
-                                DevCounters* ctr, uint64_t max_count, uint32_t* exp_rows, uint64_t exp_cap,
-                                hipStream_t st);
+// Sender side of an exchange round (k_build_winners): the owners' answers `ans` to the records `send_ref` of the
+// nshard outbox regions (`cap` slots each, counts[p] used, at most max_count in any).  exp_cap > 0: re-homing, the
+// winners go to export region p of exp_rows while it has room.
+struct WinnerArgs {
+  Layout L;
+  Ring cur;
+  uint64_t cur_base;
+  int me;
+  const uint64_t* send_ref;
+  const uint32_t* ans;
+  const uint64_t* counts;
+  int nshard;
+  uint64_t cap;
+  FrontierOut out;
+  DevCounters* ctr;
+  uint64_t max_count;
+  uint32_t* exp_rows;
+  uint64_t exp_cap;
+  hipStream_t st;
+};
+hipError_t launch_build_winners(const WinnerArgs& a);
 hipError_t launch_unpack_rows(int W, const uint32_t* rows, const uint64_t* counts, const uint64_t* bases, int nshard,
-                              uint64_t rows_cap, const Ring& next, uint64_t* parents, uint64_t next_base,
-                              uint64_t next_cap, DevCounters* ctr, uint64_t max_count, hipStream_t st);
+                              uint64_t rows_cap, const FrontierOut& out, DevCounters* ctr, uint64_t max_count,
+                              hipStream_t st);
 hipError_t launch_stage_rows(int W, const Ring& next, const uint64_t* parents, uint64_t next_base, uint64_t first,
                              uint64_t n, uint32_t* rows, hipStream_t st);
 hipError_t launch_insert_rows(const Layout& L, const uint32_t* rows, uint64_t n, uint64_t* table,

@@ -2,7 +2,7 @@
 //
 // This header is the ONE place where the spec's actions are written for the
 // product.  Every function is __host__ __device__: the GPU kernels
-// (rtla_kernels.hip) evaluate it per (state, action-instance) lane, and the
+// (csrc/*.hip) evaluate it per (state, action-instance) lane, and the
 // host driver uses the same code only to build Init and to decode rows to
 // text.  There is no CPU expansion path in the product.
 //
@@ -103,7 +103,7 @@ enum { INV_NO_TWO_LEADERS = 1, INV_ELECTION_SAFETY = 2, INV_LOG_MATCHING = 4 };
 
 // A model's row format.  Plain ints only (a C++20 structural type): the
 // kernels take it either as a run-time argument or, for the configurations
-// compiled in ahead of time (rtla_kernels.hip, LayoutSpecs), as a template
+// compiled in ahead of time (specs::, rtla_kdev.h), as a template
 // parameter -- then every offset, bound and family range below is a
 // compile-time constant in the generated code.
 struct Layout {
@@ -1295,41 +1295,6 @@ RTLA_HD void materialize(const Layout& L, P row, const DeltaT<NR>& d, R all_new,
 // row patched by a Delta, never materialised) and on the host (rows), so the
 // keys agree everywhere.
 
-// k-th permutation of 0..N-1 in lexicographic order (Lehmer code)
-template <int NS>
-RTLA_HD void kth_perm(int k, int* pi, int* inv) {
-  int avail = (1 << NS) - 1;
-  int f = 1;
-#pragma unroll
-  for (int i = 2; i < NS; i++) f *= i;  // (NS-1)!
-#pragma unroll
-  for (int i = 0; i < NS; i++) {
-    const int idx = f ? k / f : 0;
-    k -= idx * f;
-    int pick = 0, seen = -1;
-#pragma unroll
-    for (int b = 0; b < NS; b++)
-      if (avail >> b & 1) {
-        seen++;
-        if (seen == idx) pick = b;
-      }
-    pi[i] = pick;
-    avail &= ~(1 << pick);
-    if (NS - 1 - i > 0) f /= (NS - 1 - i);
-  }
-#pragma unroll
-  for (int i = 0; i < NS; i++)
-#pragma unroll
-    for (int j = 0; j < NS; j++)
-      if (pi[j] == i) inv[i] = j;
-}
-template <int NS>
-RTLA_HD uint32_t perm_mask(uint32_t m, const int* pi) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int j = 0; j < NS; j++) r |= ((m >> j) & 1u) << pi[j];
-  return r;
-}
 template <int NS>
 RTLA_HD uint32_t sel_word(const uint32_t* a, int i) {  // a[i] for a run-time i, as selects
   uint32_t r = 0;
@@ -1337,53 +1302,6 @@ RTLA_HD uint32_t sel_word(const uint32_t* a, int i) {  // a[i] for a run-time i,
   for (int k = 0; k < NS; k++)
     if (k == i) r = a[k];
   return r;
-}
-template <int NS>
-RTLA_HD uint32_t perm_id(uint32_t v, const int* pi) {  // a server id (or NIL) relabelled
-  uint32_t r = v;
-#pragma unroll
-  for (int j = 0; j < NS; j++)
-    if (v == (uint32_t)j) r = (uint32_t)pi[j];
-  return r;
-}
-// server record relabelled by pi (the record of server i, now at pi[i])
-template <int NS>
-RTLA_HD void perm_srv_rec(const uint32_t* rec, const int* pi, const int* inv, uint32_t* out) {
-  const uint32_t w0 = rec[0];
-  out[0] = s_make(s_term(w0), s_role(w0), perm_id<NS>(s_voted(w0), pi), s_commit(w0), perm_mask<NS>(s_vresp(w0), pi),
-                  perm_mask<NS>(s_vgrant(w0), pi), perm_mask<NS>(s_vlp(w0), pi));
-  out[1] = rec[1];
-  uint32_t nm = 0;
-  uint32_t vl[NS];
-#pragma unroll
-  for (int j = 0; j < NS; j++) vl[j] = rec[3 + j];
-#pragma unroll
-  for (int k = 0; k < NS; k++) {
-    const int j = inv[k];  // field k of the image = field inv[k] of the original
-    nm |= nm_next(rec[2], j) << (3 * k) | nm_match(rec[2], j) << (15 + 3 * k);
-    out[3 + k] = sel_word<NS>(vl, j);
-  }
-  out[2] = nm;
-}
-template <int NS>
-RTLA_HD uint64_t perm_msg_slot(const Layout& L, uint64_t v, const int* pi) {  // a PACKED slot relabelled
-  if (!v) return 0;  // empty slot (h_msg(0) = 0)
-  const uint64_t m = (1ull << L.b_sid) - 1ull;
-  const uint32_t src = (uint32_t)(v >> 2 & m), dst = (uint32_t)(v >> (2 + L.b_sid) & m);
-  return (v & ~(m << 2 | m << (2 + L.b_sid))) | (uint64_t)perm_id<NS>(src, pi) << 2 |
-         (uint64_t)perm_id<NS>(dst, pi) << (2 + L.b_sid);
-}
-template <int NS>
-RTLA_HD void perm_elec(const uint32_t* e, const int* pi, const int* inv, uint32_t* out) {
-  const uint32_t w0 = e[0];
-  out[0] = (w0 & 15u) | perm_id<NS>((w0 >> 4) & 7u, pi) << 4 | perm_mask<NS>((w0 >> 7) & 31u, pi) << 7 |
-           perm_mask<NS>((w0 >> 12) & 31u, pi) << 12;
-  out[1] = e[1];
-  uint32_t vl[NS];
-#pragma unroll
-  for (int j = 0; j < NS; j++) vl[j] = e[2 + j];
-#pragma unroll
-  for (int k = 0; k < NS; k++) out[2 + k] = sel_word<NS>(vl, inv[k]);
 }
 
 RTLA_HD uint32_t mix32(uint32_t x) {  // lowbias32 finalizer (signatures only)
@@ -1429,11 +1347,11 @@ RTLA_HD FP orbit_key_finish(FP m) {
 // Permutations packed 3 bits per server (pim: pi[j] at bits 3j, invm: its
 // inverse), so a loop over servers indexes them with shifts: the orbit-key
 // loops below stay rolled (one record live at a time) instead of unrolling
-// into N records' worth of registers.  Same values as the array forms above.
+// into N records' worth of registers.
 template <int NS>
 RTLA_HD uint32_t pk_get(uint32_t pm, int j) { return pm >> (3 * j) & 7u; }
 template <int NS>
-RTLA_HD uint32_t perm_id_p(uint32_t v, uint32_t pim) {
+RTLA_HD uint32_t perm_id(uint32_t v, uint32_t pim) {  // a server id (or NIL) relabelled
   uint32_t r = v;
 #pragma unroll
   for (int j = 0; j < NS; j++)
@@ -1441,18 +1359,19 @@ RTLA_HD uint32_t perm_id_p(uint32_t v, uint32_t pim) {
   return r;
 }
 template <int NS>
-RTLA_HD uint32_t perm_mask_p(uint32_t m, uint32_t pim) {
+RTLA_HD uint32_t perm_mask(uint32_t m, uint32_t pim) {
   uint32_t r = 0;
 #pragma unroll
   for (int j = 0; j < NS; j++) r |= ((m >> j) & 1u) << pk_get<NS>(pim, j);
   return r;
 }
+// server record relabelled by pi (the record of server i, now at pi[i])
 template <int NS>
-RTLA_HD void perm_srv_rec_p(const uint32_t* rec, uint32_t pim, uint32_t invm, uint32_t* out) {
+RTLA_HD void perm_srv_rec(const uint32_t* rec, uint32_t pim, uint32_t invm, uint32_t* out) {
   const uint32_t w0 = rec[0];
-  out[0] = s_make(s_term(w0), s_role(w0), perm_id_p<NS>(s_voted(w0), pim), s_commit(w0),
-                  perm_mask_p<NS>(s_vresp(w0), pim), perm_mask_p<NS>(s_vgrant(w0), pim),
-                  perm_mask_p<NS>(s_vlp(w0), pim));
+  out[0] = s_make(s_term(w0), s_role(w0), perm_id<NS>(s_voted(w0), pim), s_commit(w0),
+                  perm_mask<NS>(s_vresp(w0), pim), perm_mask<NS>(s_vgrant(w0), pim),
+                  perm_mask<NS>(s_vlp(w0), pim));
   out[1] = rec[1];
   uint32_t nm = 0;
 #pragma unroll
@@ -1464,18 +1383,18 @@ RTLA_HD void perm_srv_rec_p(const uint32_t* rec, uint32_t pim, uint32_t invm, ui
   out[2] = nm;
 }
 template <int NS>
-RTLA_HD uint64_t perm_msg_slot_p(const Layout& L, uint64_t v, uint32_t pim) {
+RTLA_HD uint64_t perm_msg_slot(const Layout& L, uint64_t v, uint32_t pim) {  // a PACKED slot relabelled
   if (!v) return 0;  // empty slot (h_msg(0) = 0)
   const uint64_t m = (1ull << L.b_sid) - 1ull;
   const uint32_t src = (uint32_t)(v >> 2 & m), dst = (uint32_t)(v >> (2 + L.b_sid) & m);
-  return (v & ~(m << 2 | m << (2 + L.b_sid))) | (uint64_t)perm_id_p<NS>(src, pim) << 2 |
-         (uint64_t)perm_id_p<NS>(dst, pim) << (2 + L.b_sid);
+  return (v & ~(m << 2 | m << (2 + L.b_sid))) | (uint64_t)perm_id<NS>(src, pim) << 2 |
+         (uint64_t)perm_id<NS>(dst, pim) << (2 + L.b_sid);
 }
 template <int NS>
-RTLA_HD void perm_elec_p(const uint32_t* e, uint32_t pim, uint32_t invm, uint32_t* out) {
+RTLA_HD void perm_elec(const uint32_t* e, uint32_t pim, uint32_t invm, uint32_t* out) {
   const uint32_t w0 = e[0];
-  out[0] = (w0 & 15u) | perm_id_p<NS>((w0 >> 4) & 7u, pim) << 4 | perm_mask_p<NS>((w0 >> 7) & 31u, pim) << 7 |
-           perm_mask_p<NS>((w0 >> 12) & 31u, pim) << 12;
+  out[0] = (w0 & 15u) | perm_id<NS>((w0 >> 4) & 7u, pim) << 4 | perm_mask<NS>((w0 >> 7) & 31u, pim) << 7 |
+           perm_mask<NS>((w0 >> 12) & 31u, pim) << 12;
   out[1] = e[1];
 #pragma unroll
   for (int k = 0; k < NS; k++) out[2 + k] = sel_word<NS>(e + 2, (int)pk_get<NS>(invm, k));
@@ -1523,14 +1442,14 @@ RTLA_HD bool sym_twins(const Layout& L, RecF rec_of, int nmsg, SlotF slot_of, in
     uint32_t a[SW], b[SW], out[SW];
     rec_of(p, a);
     rec_of(p == i ? j : p == j ? i : p, b);
-    perm_srv_rec_p<NS>(a, tau, tau, out);
+    perm_srv_rec<NS>(a, tau, tau, out);
 #pragma unroll
     for (int w = 0; w < SW; w++) same = same && out[w] == b[w];
   }
   for (int e = 0; e < nelec && same; e++) {
     uint32_t er[EW], out[EW];
     elec_of(e, er);
-    perm_elec_p<NS>(er, tau, tau, out);
+    perm_elec<NS>(er, tau, tau, out);
 #pragma unroll
     for (int w = 0; w < EW; w++) same = same && out[w] == er[w];
   }
@@ -1667,14 +1586,14 @@ RTLA_HD FP sym_image_fp(const Layout& L, RecF rec_of, int nmsg, SlotF slot_of, i
   for (int i = 0; i < NS; i++) {
     uint32_t rec[SW], out[SW];
     rec_of(i, rec);
-    perm_srv_rec_p<NS>(rec, pim, invm, out);
+    perm_srv_rec<NS>(rec, pim, invm, out);
     f = fp_add(f, hash_words_from<SW>(srv_seed<NS>((int)pk_get<NS>(pim, i)), out));
   }
-  for (int q = 0; q < nmsg; q++) f = fp_add(f, h_msg(perm_msg_slot_p<NS>(L, slot_of(q), pim)));
+  for (int q = 0; q < nmsg; q++) f = fp_add(f, h_msg(perm_msg_slot<NS>(L, slot_of(q), pim)));
   for (int e = 0; e < nelec; e++) {
     uint32_t er[EW], out[EW];
     elec_of(e, er);
-    perm_elec_p<NS>(er, pim, invm, out);
+    perm_elec<NS>(er, pim, invm, out);
     f = fp_add(f, h_elec(out, EW));
   }
   return f;
@@ -1724,27 +1643,28 @@ RTLA_HD FP orbit_key_row(const Layout& L, P row, int* perms = nullptr) {
 template <int NS, class P, class Q>
 RTLA_HD void permute_row(const Layout& L, P row, const int* pi, Q out) {
   constexpr int SW = 3 + NS, EW = 2 + NS;
-  int inv[NS];
-  for (int i = 0; i < NS; i++)
-    for (int j = 0; j < NS; j++)
-      if (pi[j] == i) inv[i] = j;
+  uint32_t pim = 0, invm = 0;  // pi and its inverse, packed
+  for (int j = 0; j < NS; j++) {
+    pim |= (uint32_t)pi[j] << (3 * j);
+    invm |= (uint32_t)j << (3 * pi[j]);
+  }
   for (int w = 0; w < L.W; w++) out[w] = row[w];
   for (int i = 0; i < NS; i++) {
     uint32_t rec[SW], img[SW];
     load_rec<NS>(L, row, i, rec);
-    perm_srv_rec<NS>(rec, pi, inv, img);
+    perm_srv_rec<NS>(rec, pim, invm, img);
     srv_put(L, out, pi[i], img);
   }
   const int nm = row_nmsg(L, row), ne = row_nelec(L, row);
   for (int q = 0; q < nm; q++) {
-    const uint64_t x = perm_msg_slot<NS>(L, slot_raw(L, row, q), pi);
+    const uint64_t x = perm_msg_slot<NS>(L, slot_raw(L, row, q), pim);
     out[L.off_bag + q * L.slot_w] = (uint32_t)x;
     if (L.slot_w > 1) out[L.off_bag + q * L.slot_w + 1] = (uint32_t)(x >> 32);
   }
   for (int e = 0; e < ne; e++) {
     uint32_t er[EW], img[EW];
     elec_get(L, row, e, er);
-    perm_elec<NS>(er, pi, inv, img);
+    perm_elec<NS>(er, pim, invm, img);
     elec_put(L, out, e, img);
   }
   row_set_fp(out, row_fingerprint(L, out));

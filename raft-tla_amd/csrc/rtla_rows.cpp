@@ -194,9 +194,13 @@ int expand_batch_dev(const Layout& L, const uint32_t* d_rows, size_t n, std::vec
     const uint64_t caps[3] = {round64(n), cap, cap};  // DevCounters cap_cur / cap_next / cap_parents
     HIPCHK(hipMemcpyAsync(&d_ctr->cap_cur, caps, sizeof caps, hipMemcpyHostToDevice, st));
     const Ring cur{const_cast<uint32_t*>(d_rows), 0, round64(n)}, next{d_out, 0, cap};
-    ShardBox box{1, 0, 0, 0, nullptr, nullptr, nullptr};
-    HIPCHK(launch_expand(L, cur, 0, n, 0, next, d_info, 0, cap, nullptr, 1, d_ctr, box, 0, st,
-                         XF_ALL_SUCCESSORS | XF_NO_COVER, nullptr));
+    HIPCHK(launch_expand({.L = L,
+                          .cur = cur,
+                          .s_end = n,
+                          .out = {next, d_info, 0, cap},
+                          .ctr = d_ctr,
+                          .st = st,
+                          .xflags = XF_ALL_SUCCESSORS | XF_NO_COVER}));
   } else {
     HIPCHK(launch_expand_batch(L, d_rows, n, d_out, d_info, cap, d_ctr, st));
   }
@@ -218,8 +222,8 @@ int expand_batch_dev(const Layout& L, const uint32_t* d_rows, size_t n, std::vec
   std::vector<size_t> ord(m);
   for (size_t k = 0; k < m; k++) ord[k] = k;
   std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
-    uint64_t ka = (info[a] >> 32) << 16 | (info[a] & 0xffff), kb = (info[b] >> 32) << 16 | (info[b] & 0xffff);
-    return ka < kb;
+    const uint64_t ia = successor_input(info[a]), ib = successor_input(info[b]);
+    return ia != ib ? ia < ib : successor_inst(info[a]) < successor_inst(info[b]);
   });
   std::vector<uint32_t> o2(m * L.W);
   std::vector<uint64_t> i2(m);
@@ -321,10 +325,18 @@ extern "C" int rtla_synthetic_dedup(rtla_ctx* x, uint64_t begin, uint64_t end, r
   s.h_caps[0] = end; s.h_caps[1] = 0; s.h_caps[2] = s.parents_cap;
   HIPCHK(hipMemcpyAsync(&s.ctr->cap_cur, s.h_caps, sizeof s.h_caps, hipMemcpyHostToDevice, x->stream));
   const Ring ring{s.arena, 0, x->front_cap};
-  ShardBox box{1, 0, 0, 0, nullptr, nullptr, nullptr};
   HIPCHK(hipEventRecord(s.ev0, x->stream));
-  HIPCHK(launch_expand(x->L, ring, begin, end, 0, ring, s.parents, 0, 0, s.table, x->tlog2, s.ctr, box, x->grid,
-                       x->stream, env_xflags() | XF_DEDUP_ONLY));
+  HIPCHK(launch_expand({.L = x->L,
+                        .cur = ring,
+                        .s_begin = begin,
+                        .s_end = end,
+                        .out = {ring, s.parents, 0, 0},
+                        .table = s.table,
+                        .tlog2 = x->tlog2,
+                        .ctr = s.ctr,
+                        .st = x->stream,
+                        .xflags = env_xflags() | XF_DEDUP_ONLY,
+                        .grid = x->grid}));
   HIPCHK(hipEventRecord(s.ev1, x->stream));
   DevCounters h;
   HIPCHK(hipMemcpyAsync(&h, s.ctr, sizeof h, hipMemcpyDeviceToHost, x->stream));
@@ -363,13 +375,21 @@ extern "C" int rtla_time_expand(rtla_ctx* x, int xflags, int reps, double* ms) {
   const uint64_t next_base = s.cur_base + s.n_cur;
   if (next_base >= s.parents_cap) return RTLA_E_OVERFLOW;
   const uint64_t next_cap = std::min<uint64_t>(next_room(x, s), s.parents_cap - next_base);
-  ShardBox box{1, 0, 0, 0, nullptr, nullptr, nullptr};
   float total = 0.f;
   for (int r = 0; r < reps; r++) {
     HIPCHK(hipMemsetAsync(s.ctr, 0, offsetof(DevCounters, cover), x->stream));
     HIPCHK(hipEventRecord(s.ev0, x->stream));
-    HIPCHK(launch_expand(x->L, cur_ring(x, s), 0, s.n_cur, s.cur_base, next_ring(x, s), s.parents, next_base,
-                         next_cap, s.table, x->tlog2, s.ctr, box, x->grid, x->stream, xflags));
+    HIPCHK(launch_expand({.L = x->L,
+                          .cur = cur_ring(x, s),
+                          .s_end = s.n_cur,
+                          .cur_base = s.cur_base,
+                          .out = {next_ring(x, s), s.parents, next_base, next_cap},
+                          .table = s.table,
+                          .tlog2 = x->tlog2,
+                          .ctr = s.ctr,
+                          .st = x->stream,
+                          .xflags = xflags,
+                          .grid = x->grid}));
     HIPCHK(hipEventRecord(s.ev1, x->stream));
     HIPCHK(hipEventSynchronize(s.ev1));
     float m = 0.f;

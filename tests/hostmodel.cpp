@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "rtla_device.h"
 #include "rtla_model.h"
 #include "rtla_plan.h"
 
@@ -29,9 +30,9 @@ int hm_layout(int n, int v, int t, int l, int c, int m, int k, int e, int inv, i
   return 0;
 }
 
-// Every enabled successor of each input row: out rows, info[k] = input index
-// << 32 | in_model << 31 | sub << 16 | instance.  Returns the count, or -1 if
-// cap is too small, -2 on a row-capacity error, -3 on a spec error.
+// Every enabled successor of each input row: out rows, info[k] = its successor
+// record (successor_info, rtla_device.h).  Returns the count, or -1 if cap is
+// too small, -2 on a row-capacity error, -3 on a spec error.
 long hm_expand(int n, int v, int t, int l, int c, int m, int k, int e, int inv, const uint32_t* rows, size_t nrows,
                uint32_t* out, uint64_t* info, size_t cap) {
   Layout L;
@@ -50,11 +51,23 @@ long hm_expand(int n, int v, int t, int l, int c, int m, int k, int e, int inv, 
       if (cnt >= cap) return -1;
       const FP cfp = fp_add(pfp, delta_fp<0>(L, row, d));
       materialize<0>(L, row, d, pall.data(), cfp, out + cnt * W);
-      info[cnt] = (uint64_t)s << 32 | (uint64_t)(d.in_model ? 1u : 0u) << 31 | (uint64_t)d.sub << 16 | (uint64_t)inst;
+      info[cnt] = successor_info(s, d.in_model, d.sub, inst);
       cnt++;
     }
   }
   return (long)cnt;
+}
+
+// The three 64-bit records (rtla_device.h): kind 0 parent record (shard, index,
+// instance), 1 successor record (input, in_model, sub, instance), 2 outbox ref
+// (parent, instance).  hm_record_fields: the accessors' view of r, in out[0..3].
+uint64_t hm_record(int kind, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+  return kind == 0 ? parent_record(a, b, c) : kind == 1 ? successor_info(a, b != 0, c, d) : outbox_ref(a, b);
+}
+void hm_record_fields(int kind, uint64_t r, uint64_t* out) {
+  out[0] = kind == 0 ? parent_shard(r) : kind == 1 ? successor_input(r) : outbox_parent(r);
+  out[1] = kind == 0 ? parent_index(r) : kind == 1 ? (uint64_t)successor_label(r) : (uint64_t)outbox_inst(r);
+  out[2] = kind == 0 ? (uint64_t)parent_inst(r) : kind == 1 ? (uint64_t)successor_inst(r) : 0;
 }
 
 // Fingerprint of a row from scratch.

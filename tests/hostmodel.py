@@ -17,7 +17,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        deps = [SRC, os.path.join(CSRC, "rtla_model.h"), os.path.join(CSRC, "rtla_plan.h")]
+        deps = [SRC, os.path.join(ROOT, "include", "rtla.h")] + [os.path.join(CSRC, h) for h in
+                                                                 ("rtla_model.h", "rtla_plan.h", "rtla_device.h")]
         if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(OUT), exist_ok=True)
             subprocess.check_call(["g++", "-O2", "-std=c++20", "-shared", "-fPIC", "-I", CSRC, "-o", OUT + ".tmp", SRC])
@@ -33,6 +34,10 @@ def lib():
         _lib.hm_plan_rehome.restype = C.c_long
         _lib.hm_plan_rebalance.argtypes = [C.c_int, u64s, u64s, u64s, C.c_size_t]
         _lib.hm_plan_rebalance.restype = C.c_long
+        _lib.hm_record.argtypes = [C.c_int] + [C.c_uint64] * 4
+        _lib.hm_record.restype = C.c_uint64
+        _lib.hm_record_fields.argtypes = [C.c_int, C.c_uint64, u64s]
+        _lib.hm_record_fields.restype = None
     return _lib
 
 

@@ -9,6 +9,7 @@
 * counterexample traces: shortest length, every step a legal transition in
   the oracle, the last state violating the invariant.
 """
+import functools
 import json
 import os
 import random
@@ -245,10 +246,15 @@ def test_shard_owner_is_a_function_of_the_projection(shape, bag):
     assert same > 100 and moved > 20
 
 
+@functools.lru_cache(maxsize=None)
+def _ntl_check():  # the small NoTwoLeaders counterexample, on the default kernel (shared: one run)
+    g = GOLD["n3_v1_t3_l1_m1_ntl"]
+    return rtla.check(cfg_of(g, **small_kw(g)))
+
+
 def test_counterexample_trace():
     g = GOLD["n3_v1_t3_l1_m1_ntl"]
-    cfg = cfg_of(g, **small_kw(g))
-    res = rtla.check(cfg)
+    res = _ntl_check()
     assert res.violation == "NoTwoLeaders"
     assert res.depth == g["depth"]
     tr = res.trace
@@ -784,6 +790,74 @@ def test_wave_kernel_matches_golden(name):
                                                                    "bfs_counts.json"), name],
                          env=env, capture_output=True, text=True, timeout=100)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+
+
+def test_wave_batch_kernel_matches_host_model(tmp_path):
+    """k_expand_batch (the parity seam and trace replay of the wave-per-state
+    path, RTLA_XFLAGS=2048 in a child process) against the host model on
+    synthetic rows that make it stage a partial 16-row batch after a full one
+    and walk a second 64-candidate chunk; and the counterexample trace it
+    replays is one the default kernel computes too (see below)."""
+    import dataclasses
+    import subprocess
+    import sys
+    import hostmodel
+    cfg = rtla.Config(**SYNTH)
+    N, V, K = cfg.n_server, cfg.n_value, cfg.bag_cap
+    fixed = 4 * N + 2 * N * N + N * V  # instances before Receive; then K Receive, K Duplicate, K Drop slots
+    assert rtla.action_name(cfg, fixed - 1, 6).startswith("AppendEntries")
+    assert rtla.action_name(cfg, fixed + 2 * K, 6) == "DropMessage" == rtla.action_name(cfg, fixed + 3 * K - 1, 6)
+    rows = rtla.random_rows(cfg, 0, 40, pool=40)
+    ref = hostmodel.expand(cfg, rows, rtla.row_words(cfg))
+    # enabled successors per (input, 64-candidate chunk): the kernel lists the fixed instances, then
+    # Receive / Duplicate / Drop over the nmsg used slots (every used slot has its Drop successor)
+    insts = {}
+    for k, inst, _, _, _ in ref:
+        insts.setdefault(k, []).append(inst)
+    per_chunk = {}
+    for k, ii in insts.items():
+        nmsg = sum(i >= fixed + 2 * K for i in ii)
+        for i in ii:
+            q = i if i < fixed else fixed + (i - fixed) // K * nmsg + (i - fixed) % K
+            per_chunk[k, q // 64] = per_chunk.get((k, q // 64), 0) + 1
+    assert any(n > 16 and n % 16 for n in per_chunk.values()), "no partial staging batch after a full one"
+    assert any(c == 1 for _, c in per_chunk), "no input with more than 64 candidates"
+    assert any(n <= 16 for n in per_chunk.values())
+
+    g = GOLD["n3_v1_t3_l1_m1_ntl"]
+    job = tmp_path / "job.json"
+    job.write_text(json.dumps({"synth": dataclasses.asdict(cfg), "rows": rows,
+                               "model": dataclasses.asdict(cfg_of(g, **small_kw(g)))}))
+    code = ("import json, rtla, sys; a = json.load(open(sys.argv[1]));"
+            "mk = lambda d: rtla.Config(**dict(d, invariants=tuple(d['invariants'])));"
+            "succ = rtla.expand_batch(mk(a['synth']), a['rows']);"
+            "res = rtla.check(mk(a['model']), trace=True);"
+            "json.dump({'succ': succ, 'violation': res.violation, 'trace': res.trace}, sys.stdout)")
+    env = dict(os.environ, RTLA_XFLAGS="2048",
+               PYTHONPATH=os.pathsep.join([os.path.join(os.path.dirname(__file__), "..", "raft-tla_amd"),
+                                           os.environ.get("PYTHONPATH", "")]))
+    out = subprocess.run([sys.executable, "-c", code, str(job)], env=env, capture_output=True, text=True, timeout=100)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    got = json.loads(out.stdout)
+    assert [tuple(t) for t in got["succ"]] == ref  # input, instance, sub, in_model, row words
+    # Which counterexample a search reports is a race (the first violation claimed, the first parent to
+    # reach a state: the wave kernel's trace differed from the default kernel's at step 1 in one run and
+    # at step 2 in another, on the library before and after the kernel-header split alike), so the two
+    # traces are compared as what they must both be: shortest counterexamples of the same invariant, the
+    # child's replayed step by step on the default kernel -- every state and label it reports is the one
+    # the level kernel computes for that action from the state before.
+    want = _ntl_check()
+    assert got["violation"] == want.violation == "NoTwoLeaders"
+    trace = [tuple(t) for t in got["trace"]]
+    assert len(trace) == len(want.trace) == g["depth"] and trace[0] == tuple(want.trace[0])
+    mcfg = cfg_of(g, **small_kw(g))
+    row = rtla.init_row(mcfg)
+    for label, text in trace[1:]:
+        nxt = [(rtla.action_name(mcfg, inst, sub), r) for _, inst, sub, _, r in rtla.expand_batch(mcfg, [row])
+               if rtla.state_text(mcfg, r) == text]
+        assert label in [n for n, _ in nxt], label
+        row = nxt[0][1]
+    assert rtla.invariants_violated(mcfg, row) & rtla.INV_BITS["NoTwoLeaders"]
 
 
 # ---- capacities: the row arena as a ring, overflow is an error, never truncation ----
