@@ -36,6 +36,12 @@
  *                            last produced ({Init} after rtla_init: TLC's plain
  *                            -simulate), so the search samples beyond the depth
  *                            the frontier arena allows.
+ *   rtla_check_frontier,
+ *   rtla_check_batch,
+ *   rtla_check_replay        TLC has no counterpart short of a second run with
+ *                            another INVARIANT list: any invariant set evaluated
+ *                            outside the search, over the states of the level
+ *                            last produced (in place in HBM) or a batch of rows.
  *   rtla_sim_replay,
  *   rtla_sim_walk            the same walks recomputed on the host from
  *                            (seed, walk id): reproduce one behaviour, as TLC
@@ -73,6 +79,8 @@ extern "C" {
 #define RTLA_INV_NO_TWO_LEADERS 1
 #define RTLA_INV_ELECTION_SAFETY 2
 #define RTLA_INV_LOG_MATCHING 4
+#define RTLA_INV_STATE_MACHINE_SAFETY 8
+#define RTLA_INV_LEADER_COMPLETENESS 16
 
 typedef struct rtla_ctx rtla_ctx;
 
@@ -271,6 +279,48 @@ int rtla_sim_replay(const rtla_cfg *cfg, const uint32_t *start_rows, size_t n_st
  * set even if cap is too small (RTLA_E_ARG). */
 int rtla_sim_walk(const rtla_cfg *cfg, const uint32_t *start_row, uint64_t seed, uint64_t walk, int32_t depth,
                   uint32_t *rows, int32_t *labels, size_t cap, size_t *n_rows);
+
+/* Audit: invariants evaluated outside the search.  inv_mask (RTLA_INV_*) is the
+ * set to evaluate, independent of cfg->inv_mask and of a context's own set.
+ * succ == 0: masks[k] = the invariants of inv_mask that rows[k] violates;
+ * succ == 1: masks[k] = the OR over every enabled successor of rows[k], in- and
+ * out-of-model, each evaluated as parent + delta as the level kernels do,
+ * without materialising it.  counts (may be NULL; 8 u64): per invariant bit
+ * (counts[b] for 1 << b), the evaluated states -- rows, or successors -- that
+ * violate it.  A spec / row-capacity error of a successor fails the call
+ * (RTLA_E_SPEC / RTLA_E_OVERFLOW).  rtla_check_batch runs on the GPU and is
+ * stateless like rtla_expand_batch (test-sized inputs); rtla_check_replay
+ * computes the same on the host, no GPU (threads: 0 = the process's CPU
+ * allowance; at most 16). */
+int rtla_check_batch(const rtla_cfg *cfg, const uint32_t *rows, size_t n, int32_t inv_mask, int32_t succ,
+                     int32_t *masks, uint64_t *counts);
+int rtla_check_replay(const rtla_cfg *cfg, const uint32_t *rows, size_t n, int32_t inv_mask, int32_t succ,
+                      int threads, int32_t *masks, uint64_t *counts);
+typedef struct {
+    uint64_t audited;      /* states audited: the rows of the frontier */
+    uint64_t evaluated;    /* states evaluated: the same (succ == 0), or their enabled successors */
+    uint64_t counts[8];    /* per invariant bit: evaluated states that violate it */
+    double kernel_ms;      /* device time of the audit (HIP events on the context's stream) */
+    uint64_t row_bytes;    /* bytes of one packed state row */
+    uint64_t viol_index;   /* the violation reported, if status == RTLA_VIOLATION: the least frontier index (as
+                              rtla_frontier numbers rows; else ~0) with a violation, ... */
+    int32_t viol_inst;     /* ... succ == 1: the least violating action instance of that row (else -1), ... */
+    int32_t viol_mask;     /* ... the RTLA_INV_* that state violates and ... */
+    int32_t viol_in_model; /* ... whether it satisfies the StateConstraint */
+    int32_t status;        /* the call's return value */
+    int32_t flags;         /* on RTLA_E_SPEC / RTLA_E_OVERFLOW: RTLA_CAP_SPEC_ERROR / RTLA_CAP_ROW */
+    int32_t reserved;
+} rtla_audit_stats;
+/* The same over the context's current frontier, in place on the GPU.  Valid
+ * where rtla_simulate is (single shard, world == 1, RTLA_MODE_BFS, a non-empty
+ * frontier, no BFS violation pending); anything else: RTLA_E_STATE.  Touches
+ * neither the fingerprint set, the arena nor the BFS counters.  Returns
+ * RTLA_OK or RTLA_VIOLATION; the violation reported does not depend on
+ * scheduling.  After RTLA_VIOLATION, rtla_violation and rtla_trace report the
+ * counterexample (the BFS parent chain from Init to the row and, succ == 1,
+ * the violating successor after it) until the next rtla_check_frontier,
+ * rtla_simulate, rtla_step or rtla_reset. */
+int rtla_check_frontier(rtla_ctx *ctx, int32_t inv_mask, int32_t succ, rtla_audit_stats *out);
 
 /* Diagnostic (performance analysis only): re-expand the current frontier
  * `reps` times with the level kernel's experiment switches `xflags` (XF_*

@@ -7,7 +7,11 @@
 //     rtla [-workers W] [-coverage M] [-gpus G] [-fpbits B] -config X.cfg SPEC.tla
 // and TLC's simulation mode (-simulate [num=N] -depth D -seed S) with
 //     rtla -simulate [num=N[,first=F]] [-depth D] [-seed S] [-bfs-levels K] -config X.cfg SPEC.tla
-// which runs K BFS levels (default 1: Init only, TLC's plain -simulate) and
+// and an audit of the last BFS level for invariants the search did not carry
+//     rtla -audit Name[,Name...] [-bfs-levels K] -config X.cfg SPEC.tla
+// (after the BFS stops -- exhausted, out of capacity, or after K levels -- the
+// named invariants are evaluated over the states of the level last produced).
+// -simulate runs K BFS levels (default 1: Init only, TLC's plain -simulate) and
 // then N random walks of up to D steps from the states of level K (walk w
 // starts at state w mod |level K|).  Walk ids are global: processes given
 // disjoint [F, F + N) ranges and the same seed explore disjoint walks, so a
@@ -16,7 +20,8 @@
 // SPEC.tla is either the reference's raft.tla (sha256 checked: the semantics
 // are compiled into the kernels, not parsed) or a wrapper module that
 // EXTENDS raft and defines the model-checking operators of specs/MC.tla
-// (StateConstraint, NoTwoLeaders, ElectionSafety, LogMatching); the raft.tla
+// (StateConstraint, NoTwoLeaders, ElectionSafety, LogMatching,
+// StateMachineSafety, LeaderCompleteness); the raft.tla
 // next to it is then hash-checked.  The cfg grammar is TLC's subset used by
 // raft.cfg: SPECIFICATION, INVARIANT(S), CONSTRAINT(S), CONSTANT(S) with
 // `Name = {a, b}` / `Name = "str"` / `Name = 3` / `Name = mv`, and \* / (* *)
@@ -205,10 +210,14 @@ void usage() {
           "            [-raft PATH/raft.tla] [-skip-spec-check]\n"
           "            [-checkpoint MINUTES] [-checkpointdir PREFIX] [-recover PREFIX]\n"
           "            [-simulate [num=N[,first=F]]] [-depth D] [-seed S] [-bfs-levels K]\n"
+          "            [-audit Name[,Name...]]\n"
           "            -config FILE.cfg SPEC.tla\n"
           "  -simulate: after K BFS levels (default 1 = Init only) run N random walks (default 1000000) of up to\n"
           "  D steps (default 100) from the states of level K; walk ids F .. F+N-1 are global, so runs with\n"
-          "  disjoint ranges and the same seed compose; one GPU only.\n");
+          "  disjoint ranges and the same seed compose; one GPU only.\n"
+          "  -audit: when the BFS stops (exhausted, out of capacity, or after -bfs-levels K) evaluate the named\n"
+          "  invariants -- any of the specification's, not only the cfg's -- over the states of the last level;\n"
+          "  one GPU only.\n");
 }
 
 std::string subst_names(const std::string& s, const std::vector<std::string>& servers,
@@ -334,6 +343,19 @@ bool rendezvous(int rank, const char* path, bool dry, unsigned char id[128]) {
   return false;
 }
 
+// The invariants of specs/MC.tla, in RTLA_INV_* bit order.
+const struct { const char* name; int32_t bit; } INVARIANTS[] = {
+    {"NoTwoLeaders", RTLA_INV_NO_TWO_LEADERS},
+    {"ElectionSafety", RTLA_INV_ELECTION_SAFETY},
+    {"LogMatching", RTLA_INV_LOG_MATCHING},
+    {"StateMachineSafety", RTLA_INV_STATE_MACHINE_SAFETY},
+    {"LeaderCompleteness", RTLA_INV_LEADER_COMPLETENESS}};
+int32_t invariant_bit(const std::string& name) {
+  for (auto& i : INVARIANTS)
+    if (name == i.name) return i.bit;
+  return 0;
+}
+
 const char* COVER[] = {"Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
                        "AdvanceCommitIndex", "AppendEntries", "Receive", "DuplicateMessage", "DropMessage",
                        "UpdateTerm", "HandleRequestVoteRequest", "HandleRequestVoteResponse",
@@ -354,6 +376,10 @@ int main(int argc, char** argv) {
   uint64_t sim_num = 1000000, sim_first = 0, sim_seed = 0;
   bool have_seed = false;
   int sim_depth = 100, bfs_levels = 1;
+  bool have_levels = false;
+  // -audit Name[,Name...]: invariants evaluated over the last BFS level
+  bool audit = false;
+  std::vector<std::string> audit_names;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -385,7 +411,13 @@ int main(int argc, char** argv) {
     }
     else if (a == "-depth") sim_depth = atoi(next().c_str());
     else if (a == "-seed") { sim_seed = strtoull(next().c_str(), nullptr, 10); have_seed = true; }
-    else if (a == "-bfs-levels") bfs_levels = atoi(next().c_str());
+    else if (a == "-bfs-levels") { bfs_levels = atoi(next().c_str()); have_levels = true; }
+    else if (a == "-audit") {
+      audit = true;
+      std::stringstream names(next());
+      for (std::string nm; std::getline(names, nm, ',');)
+        if (!nm.empty()) audit_names.push_back(nm);
+    }
     else if (a == "-h" || a == "-help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { fprintf(stderr, "Error: unsupported option %s\n", a.c_str()); return 255; }
     else spec = a;
@@ -395,6 +427,14 @@ int main(int argc, char** argv) {
   if (simulate && gpus > 1) {
     fprintf(stderr, "Error: -simulate runs on one GPU; split the walks over processes instead "
                     "(-simulate num=N,first=F with disjoint ranges and the same -seed)\n");
+    return 255;
+  }
+  if (audit && (gpus > 1 || simulate || audit_names.empty())) {
+    fprintf(stderr, "Error: -audit names at least one invariant and runs on one GPU, without -simulate\n");
+    return 255;
+  }
+  if (audit && bfs_levels < 1) {
+    fprintf(stderr, "Error: -bfs-levels must be at least 1\n");
     return 255;
   }
   if (simulate && (sim_depth < 0 || sim_depth > 65535 || bfs_levels < 1)) {
@@ -462,7 +502,7 @@ int main(int argc, char** argv) {
   // Operators available: raft.tla defines none of the MC operators.
   auto defined = [&](const std::string& op) {
     if (!wrapper) return false;
-    return op == "StateConstraint" || op == "NoTwoLeaders" || op == "ElectionSafety" || op == "LogMatching";
+    return op == "StateConstraint" || invariant_bit(op) != 0;
   };
   rtla_cfg c;
   memset(&c, 0, sizeof c);
@@ -472,8 +512,16 @@ int main(int argc, char** argv) {
              inv.c_str());
       return 150;
     }
-    c.inv_mask |= inv == "NoTwoLeaders" ? RTLA_INV_NO_TWO_LEADERS : inv == "ElectionSafety" ? RTLA_INV_ELECTION_SAFETY
-                                                                                        : RTLA_INV_LOG_MATCHING;
+    c.inv_mask |= invariant_bit(inv);
+  }
+  int32_t audit_mask = 0;
+  for (auto& inv : audit_names) {
+    if (!defined(inv) || inv == "StateConstraint") {
+      printf("Error: The invariant %s specified in the configuration file is not defined in the specification.\n",
+             inv.c_str());
+      return 150;
+    }
+    audit_mask |= invariant_bit(inv);
   }
   for (auto& k : cf.constraints) {
     if (k != "StateConstraint" || !defined(k)) {
@@ -557,7 +605,9 @@ int main(int argc, char** argv) {
   // everywhere: the clock is then the job's device time (the per-level
   // maximum over ranks, identical on every rank), not this rank's wall clock.
   double dev_s = 0, dev_ckpt = 0;
-  while (st == RTLA_OK && !(simulate && ls.level >= bfs_levels)) {
+  // -bfs-levels K stops the search for what follows it: the walks, or the audit
+  const bool stop_at_level = simulate || (audit && have_levels);
+  while (st == RTLA_OK && !(stop_at_level && ls.level >= bfs_levels)) {
     st = rtla_step(ctx, &ls);
     if (st < 0) break;
     dev_s += ls.kernel_ms / 1e3;
@@ -591,10 +641,44 @@ int main(int argc, char** argv) {
   }
   double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   int exit_code = 0;
-  if (st < 0) {
+  // -audit after a search that ran out of capacity: the level last completed is still the frontier
+  const bool audit_after_overflow = audit && st == RTLA_E_OVERFLOW;
+  if (audit_after_overflow) {
+    printf("Warning: %s (%s) while producing level %d; the search stops here.\n", rtla_strerror(st),
+           ls.flags & RTLA_CAP_FRONTIER ? "frontier" : ls.flags & RTLA_CAP_FPSET ? "fingerprint set" : "row / outbox",
+           ls.level);
+    ls.level--;  // (the level that did not complete is dropped)
+  } else if (st < 0) {
     printf("Error: %s\n", rtla_strerror(st));
     rtla_close(ctx);
     return 255;
+  }
+  // -audit: the BFS stopped (exhausted: the last non-empty level is gone, so there is nothing to audit)
+  bool audited = false;
+  if (audit && (st == RTLA_OK || audit_after_overflow)) {
+    size_t nfront = 0;
+    rtla_frontier(ctx, nullptr, 0, &nfront);
+    if (audit_after_overflow) ls.new_states = nfront;  // still on the queue
+    rtla_audit_stats as;
+    memset(&as, 0, sizeof as);
+    st = rtla_check_frontier(ctx, audit_mask, 0, &as);
+    if (st < 0) {
+      printf("Error: audit: %s\n", rtla_strerror(st));
+      rtla_close(ctx);
+      return 255;
+    }
+    audited = true;
+    printf("Auditing the %llu states of BFS level %d: %.3f ms on the GPU.\n", (unsigned long long)as.audited,
+           ls.level, as.kernel_ms);
+    for (int b = 0; b < (int)(sizeof INVARIANTS / sizeof INVARIANTS[0]); b++)
+      if (audit_mask & INVARIANTS[b].bit) {
+        if (as.counts[b]) printf("Error: Invariant %s is violated by %llu of the %llu states.\n", INVARIANTS[b].name,
+                                 (unsigned long long)as.counts[b], (unsigned long long)as.audited);
+        else printf("Invariant %s holds in all %llu states.\n", INVARIANTS[b].name, (unsigned long long)as.audited);
+      }
+    secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  } else if (audit && st == RTLA_DONE) {
+    printf("Audit: the search is complete and its last level is empty; nothing to audit.\n");
   }
   // -simulate: the BFS stopped at level K with nothing found (a BFS that
   // finished or violated first is reported below as without -simulate)
@@ -633,8 +717,8 @@ int main(int argc, char** argv) {
   if (st == RTLA_VIOLATION) {
     int32_t mask = 0, inm = 0;
     rtla_violation(ctx, &mask, &inm);
-    const char* inv = mask & RTLA_INV_NO_TWO_LEADERS ? "NoTwoLeaders" : mask & RTLA_INV_ELECTION_SAFETY ? "ElectionSafety" : "LogMatching";
-    printf("Error: Invariant %s is violated.\n", inv);
+    for (auto& i : INVARIANTS)  // every violated name, in bit order
+      if (mask & i.bit) printf("Error: Invariant %s is violated.\n", i.name);
     printf("Error: The behavior up to this point is:\n");
     size_t n = 0;
     rtla_trace(ctx, nullptr, nullptr, 0, &n);
@@ -656,6 +740,8 @@ int main(int argc, char** argv) {
       }
     }
     exit_code = 12;
+  } else if (audited) {
+    printf("Audit completed. No error has been found in the audited level (not an exhaustive search).\n");
   } else if (simulated) {
     printf("Simulation completed. No error has been found in %d BFS levels and the walks above "
            "(not an exhaustive search).\n", ls.level);
@@ -684,8 +770,9 @@ int main(int argc, char** argv) {
   }
   printf("%llu states generated, %llu distinct states found, %llu states left on queue.\n",
          (unsigned long long)ls.generated_total, (unsigned long long)ls.distinct_total,
-         (unsigned long long)(simulated ? ls.new_states : 0));
-  if (simulated) printf("The depth of the breadth-first search before the simulation is %d.\n", depth);
+         (unsigned long long)(simulated || audited ? ls.new_states : 0));
+  if (audited) printf("The depth of the breadth-first search before the audit is %d.\n", depth);
+  else if (simulated) printf("The depth of the breadth-first search before the simulation is %d.\n", depth);
   else printf("The depth of the complete state graph search is %d.\n", depth);
   printf("Finished in %.2fs at (%s)\n", secs, now_str().c_str());
   rtla_close(ctx);

@@ -3,6 +3,7 @@
 //   rtla_comm.cpp     collectives and transfers between shards (RCCL, shared memory, device copies)
 //   rtla_ckpt.cpp     checkpoint / recover
 //   rtla_simhost.cpp  random-walk simulation
+//   rtla_audit.cpp    invariants outside the search: batch, host replay, frontier audit
 //   rtla_rows.cpp     the context-free row API, synthetic and probe micro-benchmarks
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 
 #include "../../include/rtla.h"
 #include "rtla_device.h"
+#include "rtla_audit.h"
 #include "rtla_launch.h"
 #include "rtla_model.h"
 
@@ -75,6 +77,16 @@ struct SimState {
   int step = 0, inst = -1, mask = 0, in_model = 0;
 };
 
+// rtla_check_frontier's device counters and events (allocated at first use)
+// and the violation its last call found (rtla_violation / rtla_trace).
+struct AuditState {
+  AuditCounters* ctr = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool viol = false;
+  uint64_t start = 0;  // parent-record index of the violating row (succ: of the violating successor's parent)
+  int inst = -1, mask = 0, in_model = 0;  // inst >= 0: the violating successor's action instance
+};
+
 // device scratch of the all-reduces: sums at [0, RED_MAX_AT), maxima after
 constexpr int RED_WORDS = 256, RED_MAX_AT = 192;
 
@@ -109,6 +121,7 @@ struct rtla_ctx {
   int grid = 0;
   std::vector<uint32_t> init_row;
   SimState sim;
+  AuditState audit;
 
   Shard* local(int id) {  // the shard with this global id, if this process holds it
     for (auto& s : sh)

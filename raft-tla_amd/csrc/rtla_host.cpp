@@ -148,6 +148,9 @@ extern "C" void rtla_close(rtla_ctx* x) {
     if (p) (void)hipFree(p);
   if (x->sim.ev0) (void)hipEventDestroy(x->sim.ev0);
   if (x->sim.ev1) (void)hipEventDestroy(x->sim.ev1);
+  if (x->audit.ctr) (void)hipFree(x->audit.ctr);
+  if (x->audit.ev0) (void)hipEventDestroy(x->audit.ev0);
+  if (x->audit.ev1) (void)hipEventDestroy(x->audit.ev1);
   comm_close(x);
   if (x->stream) (void)hipStreamDestroy(x->stream);
   delete x;
@@ -389,6 +392,7 @@ extern "C" int rtla_reset(rtla_ctx* x) {
   HIPCHK(hipStreamSynchronize(x->stream));
   x->inited = false; x->finished = false; x->level = 0; x->distinct = 0; x->generated = 0; x->max_front = 0;
   x->sim.viol = false;
+  x->audit.viol = false;
   return RTLA_OK;
 }
 
@@ -956,6 +960,7 @@ extern "C" int rtla_step(rtla_ctx* x, rtla_level_stats* st) {
   if (!x) return RTLA_E_ARG;
   if (!x->inited || x->finished) return RTLA_E_STATE;
   x->sim.viol = false;  // (a simulated violation is the last rtla_simulate's: the BFS goes on as if it had not run)
+  x->audit.viol = false;  // (and an audit's the last rtla_check_frontier's)
   const double t0 = now_s();
   HIPCHK(hipSetDevice(x->device));
   Level lv;
@@ -970,9 +975,9 @@ extern "C" int rtla_step(rtla_ctx* x, rtla_level_stats* st) {
 
 extern "C" int rtla_violation(rtla_ctx* x, int32_t* inv_mask, int32_t* in_model) {
   if (!x) return RTLA_E_ARG;
-  if (x->sim.viol) {
-    if (inv_mask) *inv_mask = x->sim.mask;
-    if (in_model) *in_model = x->sim.in_model;
+  if (x->sim.viol || x->audit.viol) {
+    if (inv_mask) *inv_mask = x->sim.viol ? x->sim.mask : x->audit.mask;
+    if (in_model) *in_model = x->sim.viol ? x->sim.in_model : x->audit.in_model;
     return RTLA_VIOLATION;
   }
   Shard* s = x->viol_shard();
@@ -1114,6 +1119,8 @@ static int trace_start(rtla_ctx* x, bool bad, uint64_t start[4]) {
   Shard* vs = x->viol_shard();
   if (x->sim.viol) {  // (single shard, world 1: rtla_simulate's precondition)
     start[0] = 1; start[1] = 0; start[2] = x->sim.start; start[3] = 0;
+  } else if (x->audit.viol) {  // (the same precondition: the audited row, or its violating successor)
+    start[0] = 1; start[1] = 0; start[2] = x->audit.start; start[3] = (uint64_t)(x->audit.inst + 1);
   } else if (vs) {
     start[0] = 1;
     start[1] = (uint64_t)vs->id;

@@ -1,0 +1,177 @@
+// rtla_kaudit.hip -- the audit kernels: invariants evaluated outside the
+// search, over a batch of rows or over the frontier in HBM (semantics in
+// rtla_audit.h; the host replay computes the same masks, counts and key).
+//   * k_audit_state: the rows themselves.  A pure stream over the rows: a wave
+//     takes 64 consecutive rows (a group never wraps the ring), copies them
+//     into LDS with 16-byte loads, coalesced, and each lane then evaluates its
+//     own row there -- the row stride W is odd, so the 64 lanes' reads of word
+//     k fall on different banks.  Rows too wide for 64 to fit are staged in
+//     tiles of `tr` rows.
+//   * k_audit_succ: every enabled successor.  k_expand's shape (rtla_kwave.hip)
+//     with the set, the row building and the outbox removed: one wave per
+//     state, the row in LDS, each lane evaluates one action instance as a
+//     Delta and checks parent + delta.
+// Both count per invariant bit with ballots into wave-uniform registers, add
+// them to the block's LDS tally once per wave and to the device counters once
+// per block, and report the least violation key with one atomicMin per wave.
+#include "rtla_kdev.h"
+#include "rtla_audit.h"
+
+namespace {
+
+constexpr int AUDIT_HEAD = 8;  // the block's tally: u32 words at the start of the dynamic LDS (32 bytes)
+
+// Rows of a k_audit_state staging tile: the most (a power of two <= 64) that fit in 12 KB per wave
+// (four waves: 48 KB of the 64 KB a block may ask for; configs[1]'s 43-word rows take 10.75 KB).
+__host__ __device__ constexpr int audit_tile_rows(int W) {
+  int tr = 64;
+  while (tr > 4 && tr * W * 4 > 12288) tr >>= 1;
+  return tr;
+}
+
+// Per-bit ballots of `bad` added to the wave-uniform counts; returns the OR over the wave.
+__device__ __forceinline__ int audit_count(int bad, unsigned int (&cnt)[INV_COUNT]) {
+  int any = 0;
+#pragma unroll
+  for (int k = 0; k < INV_COUNT; k++) {
+    const int c = __popcll(__ballot(bad >> k & 1));
+    cnt[k] += (unsigned int)c;
+    any |= c ? 1 << k : 0;
+  }
+  return any;
+}
+
+// End of kernel: the wave's counts -> the block's LDS tally -> the device counters; the wave's least key.
+__device__ __forceinline__ void audit_finish(unsigned int* tally, const unsigned int (&cnt)[INV_COUNT],
+                                             unsigned long long evaluated, unsigned long long vkey, AuditCounters* ctr,
+                                             int lane) {
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < INV_COUNT; k++)
+      if (cnt[k]) atomicAdd(&tally[k], cnt[k]);
+    if (evaluated) atomicAdd(&ctr->evaluated, evaluated);
+    if (vkey != AUDIT_NO_VIOLATION) atomicMin(&ctr->viol_key, vkey);
+  }
+  cover_flush(tally, INV_COUNT, ctr->counts);
+}
+
+}  // namespace
+
+// Rows [0, n) of `cur`; masks (may be null): the violated mask of each row.
+// (A wave's counts are u32: a wave sees far fewer than 2^32 rows.)
+template <int NS>
+__global__ void __launch_bounds__(256)
+k_audit_state(Layout L, Ring cur, unsigned long long n, int tr, int* __restrict__ masks, AuditCounters* ctr) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int W = L.W;
+  uint32_t* const tile = lds + AUDIT_HEAD + wave * tr * W;
+  cover_zero(lds, AUDIT_HEAD);
+
+  unsigned int cnt[INV_COUNT] = {};
+  unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
+  const unsigned long long ngroup = (n + 63) >> 6;
+  for (unsigned long long g = (unsigned long long)blockIdx.x * wpb + wave; g < ngroup;
+       g += (unsigned long long)gridDim.x * wpb) {
+    const int nv = (int)min<unsigned long long>(64ull, n - (g << 6));
+    for (int r0 = 0; r0 < nv; r0 += tr) {
+      const int nt = min(tr, nv - r0);
+      const unsigned long long first = (g << 6) + r0;
+      copy_words_lds16(tile, ring_row(cur, first, W), nt * W, lane);
+      wave_sync();
+      int bad = 0;
+      if (lane < nt) {
+        bad = check_invariants_v<NS>(L, (const uint32_t*)(tile + lane * W), -1, 0u, 0u, 0, 0u);
+        if (masks) masks[first + lane] = bad;
+      }
+      const unsigned long long mb = __ballot(bad != 0);
+      if (mb) {
+        audit_count(bad, cnt);
+        if (vkey == AUDIT_NO_VIOLATION) {  // groups and tiles ascend: the wave's first is its least
+          const int fl = __builtin_ctzll(mb);
+          vkey = audit_key(first + fl, 0, 1, __shfl(bad, fl));
+        }
+      }
+      evaluated += nt;
+      wave_sync();
+    }
+  }
+  audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
+}
+
+// Every enabled successor of rows [0, n) of `cur`; masks (may be null): the OR over each row's successors.
+template <int NS>
+__global__ void __launch_bounds__(256)
+k_audit_succ(Layout L, Ring cur, unsigned long long n, int* __restrict__ masks, AuditCounters* ctr) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int W = L.W;
+  uint32_t* const prow = lds + AUDIT_HEAD + wave * even_words(W);
+  cover_zero(lds, AUDIT_HEAD);
+
+  unsigned int cnt[INV_COUNT] = {};
+  unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
+  const int fixed = L.fam[F_RECEIVE];
+  for (unsigned long long s = (unsigned long long)blockIdx.x * wpb + wave; s < n;
+       s += (unsigned long long)gridDim.x * wpb) {
+    const uint32_t* __restrict__ src = ring_row(cur, s, W);
+    for (int w = lane; w < W; w += 64) prow[w] = src[w];
+    wave_sync();
+    const int nmsg = row_nmsg(L, prow);
+    const int ncand = fixed + 3 * nmsg;
+    int all = 0;
+    bool found = false;
+    for (int base = 0; base < ncand; base += 64) {
+      const int q = base + lane;
+      DeltaT<NS> d;
+      d.enabled = 0;
+      d.in_model = 0;
+      int inst = 0;
+      if (q < ncand) {
+        inst = candidate_inst(L, q, nmsg);
+        compute_delta<NS>(L, prow, inst, d);
+      }
+      const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
+      evaluated += __popcll(__ballot(en));
+      const int bad = en ? check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]) : 0;
+      const unsigned long long mb = __ballot(bad != 0);
+      if (mb) {
+        all |= audit_count(bad, cnt);
+        if (!found) {  // the row's least violating instance: instances ascend with q
+          found = true;
+          const int fl = __builtin_ctzll(mb);
+          const unsigned long long key = audit_key(s, __shfl(inst, fl), __shfl((int)d.in_model, fl), __shfl(bad, fl));
+          if (key < vkey) vkey = key;
+        }
+      }
+    }
+    if (masks && lane == 0) masks[s] = all;
+    wave_sync();
+  }
+  audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
+}
+
+namespace rtla {
+
+hipError_t launch_audit(const Layout& L, const Ring& cur, uint64_t n, int succ, int* masks, AuditCounters* ctr,
+                        hipStream_t st) {
+  if (!n) return hipSuccess;
+  const int wpb = 4;
+  if (succ) {
+    const unsigned grid = (unsigned)std::min<uint64_t>((n + wpb - 1) / wpb, (uint64_t)device_cus() * 16);
+    const size_t lds = (size_t)(AUDIT_HEAD + wpb * even_words(L.W)) * sizeof(uint32_t);
+    RTLA_DISPATCH_N(L, k_audit_succ, dim3(grid), dim3(64 * wpb), lds, st, L, cur, (unsigned long long)n, masks, ctr);
+  } else {
+    const int tr = audit_tile_rows(L.W);
+    const uint64_t ngroup = (n + 63) / 64;
+    const unsigned grid = (unsigned)std::min<uint64_t>((ngroup + wpb - 1) / wpb, (uint64_t)device_cus() * 8);
+    const size_t lds = (size_t)(AUDIT_HEAD + wpb * tr * L.W) * sizeof(uint32_t);
+    RTLA_DISPATCH_N(L, k_audit_state, dim3(grid), dim3(64 * wpb), lds, st, L, cur, (unsigned long long)n, tr, masks,
+                    ctr);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace rtla

@@ -79,6 +79,11 @@ size_t simulate_lds_bytes(const Layout& L, int wpb);
 hipError_t launch_simulate(const Layout& L, const Ring& cur, uint64_t n_front, uint64_t seed, uint64_t first,
                            uint32_t n_walks, int t0, int t1, int depth, uint32_t* carry, uint64_t* ends,
                            SimCounters* ctr, hipStream_t st);
+// The audit (rtla_kaudit.hip, rtla_audit.h): L.inv_mask evaluated on rows [0, n) of `cur` (succ 0) or on their
+// enabled successors (succ 1); masks (n ints) may be null; ctr: counts added, least violation key kept.
+struct AuditCounters;
+hipError_t launch_audit(const Layout& L, const Ring& cur, uint64_t n, int succ, int* masks, AuditCounters* ctr,
+                        hipStream_t st);
 hipError_t launch_insert_remote(const uint64_t* recv_fp, const uint64_t* counts, int nshard, uint64_t cap,
                                 uint64_t* table, int tlog2, uint32_t* ans, DevCounters* ctr, uint64_t max_count,
                                 hipStream_t st);

@@ -99,7 +99,11 @@ enum {
 };
 
 // Invariant bits (build-defined model wrapper, specs/MC.tla).
-enum { INV_NO_TWO_LEADERS = 1, INV_ELECTION_SAFETY = 2, INV_LOG_MATCHING = 4 };
+enum {
+  INV_NO_TWO_LEADERS = 1, INV_ELECTION_SAFETY = 2, INV_LOG_MATCHING = 4,
+  INV_STATE_MACHINE_SAFETY = 8, INV_LEADER_COMPLETENESS = 16,
+  INV_COUNT = 5, INV_ALL = 31
+};
 
 // A model's row format.  Plain ints only (a C++20 structural type): the
 // kernels take it either as a run-time argument or, for the configurations
@@ -1718,6 +1722,37 @@ RTLA_HD int check_invariants_v(const Layout& L, P row, int dsrv, uint32_t drec0,
         const uint32_t m = log_len(a) < log_len(b) ? log_len(a) : log_len(b);
         for (uint32_t n = 1; n <= m; n++)
           if (log_term(a, n) == log_term(b, n) && log_prefix(a, n) != log_prefix(b, n)) bad |= INV_LOG_MATCHING;
+      }
+  }
+  if (L.inv_mask & INV_STATE_MACHINE_SAFETY) {
+    // StateMachineSafety == \A i, j \in Server : \A n \in 1..Min({commitIndex[i], commitIndex[j]}) :
+    //   (n <= Len(log[i]) /\ n <= Len(log[j])) => log[i][n] = log[j][n]
+    // -- the entries are compared index by index, so: the prefixes of the least of the four lengths are equal
+#pragma unroll
+    for (int i = 0; i < NC; i++)
+#pragma unroll
+      for (int j = i + 1; j < NC; j++) {
+        if (j >= N) continue;
+        const uint32_t a = lg[i], b = lg[j];
+        uint32_t m = s_commit(w0[i]) < s_commit(w0[j]) ? s_commit(w0[i]) : s_commit(w0[j]);
+        if (log_len(a) < m) m = log_len(a);
+        if (log_len(b) < m) m = log_len(b);
+        if (log_prefix(a, m) != log_prefix(b, m)) bad |= INV_STATE_MACHINE_SAFETY;
+      }
+  }
+  if (L.inv_mask & INV_LEADER_COMPLETENESS) {
+    // LeaderCompleteness == \A i, j \in Server : (state[i] = Leader /\ currentTerm[j] <= currentTerm[i]) =>
+    //   \A n \in 1..commitIndex[j] : n <= Len(log[j]) => (n <= Len(log[i]) /\ log[i][n] = log[j][n])
+    // -- with m the committed entries j holds: the leader's log has m entries and the same first m
+#pragma unroll
+    for (int i = 0; i < NC; i++)
+#pragma unroll
+      for (int j = 0; j < NC; j++) {
+        if (i >= N || j >= N || j == i) continue;
+        if (s_role(w0[i]) != LEADER || s_term(w0[j]) > s_term(w0[i])) continue;
+        const uint32_t a = lg[i], b = lg[j];
+        const uint32_t m = s_commit(w0[j]) < log_len(b) ? s_commit(w0[j]) : log_len(b);
+        if (m > log_len(a) || log_prefix(a, m) != log_prefix(b, m)) bad |= INV_LEADER_COMPLETENESS;
       }
   }
   return bad;

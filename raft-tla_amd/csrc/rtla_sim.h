@@ -48,12 +48,18 @@ RTLA_HD uint64_t sim_path_term(FP f, uint32_t t) {
 
 RTLA_HD uint64_t sim_end_word(uint32_t length, int stop) { return (uint64_t)length | (uint64_t)stop << 32; }
 
-// Violation key, least first: walk (its index in the batch) << 36 | step << 20
-// | instance << 4 | in_model << 3 | violated-invariant mask.  The low four
-// bits are a function of (walk, step, instance), so the order is theirs.
+// Violation key, least first: walk (its index in the batch, < 2^18) << 38 |
+// step << 22 | instance << 6 | in_model << 5 | violated-invariant mask.  The
+// low six bits are a function of (walk, step, instance), so the order is theirs.
 RTLA_HD uint64_t sim_viol_key(uint64_t rel_walk, uint32_t step, int inst, int in_model, int mask) {
-  return rel_walk << 36 | (uint64_t)step << 20 | (uint64_t)inst << 4 | (uint64_t)(in_model ? 8 : 0) | (uint64_t)(mask & 7);
+  return rel_walk << 38 | (uint64_t)step << 22 | (uint64_t)inst << 6 | (uint64_t)(in_model ? 32 : 0) |
+         (uint64_t)(mask & INV_ALL);
 }
+RTLA_HD uint64_t sim_key_walk(uint64_t key) { return key >> 38; }
+RTLA_HD int sim_key_step(uint64_t key) { return (int)(key >> 22 & 0xffff); }
+RTLA_HD int sim_key_inst(uint64_t key) { return (int)(key >> 6 & 0xffff); }
+RTLA_HD int sim_key_in_model(uint64_t key) { return (int)(key >> 5 & 1); }
+RTLA_HD int sim_key_mask(uint64_t key) { return (int)(key & INV_ALL); }
 
 RTLA_HD int sim_cover_code(const Layout& L, int inst, int sub) {  // the level kernels' cover_code
   int fam = 0;

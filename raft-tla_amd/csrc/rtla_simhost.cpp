@@ -19,11 +19,11 @@ static void sim_fill_stats(rtla_sim_stats* st, uint64_t walks, const SimTally& t
   st->kernel_ms = ms; st->status = status; st->flags = t.flags;
   st->viol_walk = ~0ull; st->viol_inst = -1;
   if (t.viol_key != SIM_NO_VIOLATION) {
-    st->viol_walk = batch_first + (t.viol_key >> 36);
-    st->viol_step = (int32_t)(t.viol_key >> 20 & 0xffff);
-    st->viol_inst = (int32_t)(t.viol_key >> 4 & 0xffff);
-    st->viol_in_model = (int32_t)(t.viol_key >> 3 & 1);
-    st->viol_mask = (int32_t)(t.viol_key & 7);
+    st->viol_walk = batch_first + sim_key_walk(t.viol_key);
+    st->viol_step = sim_key_step(t.viol_key);
+    st->viol_inst = sim_key_inst(t.viol_key);
+    st->viol_in_model = sim_key_in_model(t.viol_key);
+    st->viol_mask = sim_key_mask(t.viol_key);
   }
   static_assert(sizeof st->taken / sizeof st->taken[0] == COVER_CODES, "rtla_sim_stats.taken holds every coverage code");
   for (int k = 0; k < COVER_CODES; k++) st->taken[k] = t.taken[k];
@@ -123,6 +123,7 @@ extern "C" int rtla_simulate(rtla_ctx* x, uint64_t seed, uint64_t first_walk, ui
   Shard& s = x->sh[0];
   SimState& m = x->sim;
   m.viol = false;
+  x->audit.viol = false;
   if (!m.ctr) HIPCHK(hipMalloc((void**)&m.ctr, sizeof(SimCounters)));
   if (!m.ev0) HIPCHK(hipEventCreate(&m.ev0));
   if (!m.ev1) HIPCHK(hipEventCreate(&m.ev1));
@@ -182,12 +183,12 @@ extern "C" int rtla_simulate(rtla_ctx* x, uint64_t seed, uint64_t first_walk, ui
   if (status == RTLA_VIOLATION) {
     m.viol = true;
     m.seed = seed;
-    m.walk = viol_first + (sum.viol_key >> 36);
+    m.walk = viol_first + sim_key_walk(sum.viol_key);
     m.start = s.cur_base + m.walk % s.n_cur;
-    m.step = (int)(sum.viol_key >> 20 & 0xffff);
-    m.inst = (int)(sum.viol_key >> 4 & 0xffff);
-    m.in_model = (int)(sum.viol_key >> 3 & 1);
-    m.mask = (int)(sum.viol_key & 7);
+    m.step = sim_key_step(sum.viol_key);
+    m.inst = sim_key_inst(sum.viol_key);
+    m.in_model = sim_key_in_model(sum.viol_key);
+    m.mask = sim_key_mask(sum.viol_key);
   }
   return status;
 }

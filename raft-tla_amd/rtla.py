@@ -24,7 +24,8 @@ LIB_PATH = os.environ.get("RTLA_LIB") or os.path.join(HERE, "librtla.so")  # RTL
 
 OK, DONE, VIOLATION = 0, 1, 2
 E_CONFIG, E_HIP, E_OVERFLOW, E_SPEC, E_STATE, E_ARG, E_COMM = -1, -2, -3, -4, -5, -6, -7  # include/rtla.h
-INV_BITS = {"NoTwoLeaders": 1, "ElectionSafety": 2, "LogMatching": 4}
+INV_BITS = {"NoTwoLeaders": 1, "ElectionSafety": 2, "LogMatching": 4, "StateMachineSafety": 8,
+            "LeaderCompleteness": 16}  # specs/MC.tla; in bit order
 COVER_NAMES = ["Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
                "AdvanceCommitIndex", "AppendEntries", "Receive", "DuplicateMessage",
                "DropMessage", "UpdateTerm", "HandleRequestVoteRequest",
@@ -68,6 +69,13 @@ class _SimStats(C.Structure):
                 ("kernel_ms", C.c_double), ("viol_walk", C.c_uint64), ("viol_step", C.c_int32),
                 ("viol_inst", C.c_int32), ("viol_mask", C.c_int32), ("viol_in_model", C.c_int32),
                 ("status", C.c_int32), ("flags", C.c_int32), ("taken", C.c_uint64 * 16)]
+
+
+class _AuditStats(C.Structure):
+    _fields_ = [("audited", C.c_uint64), ("evaluated", C.c_uint64), ("counts", C.c_uint64 * 8),
+                ("kernel_ms", C.c_double), ("row_bytes", C.c_uint64), ("viol_index", C.c_uint64),
+                ("viol_inst", C.c_int32), ("viol_mask", C.c_int32), ("viol_in_model", C.c_int32),
+                ("status", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 def _load():
@@ -127,6 +135,11 @@ def _load():
                                       C.c_int32, C.c_int, P(C.c_uint64), P(_SimStats)]),
         "rtla_sim_walk": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_uint64, C.c_uint64, C.c_int32, P(C.c_uint32),
                                     P(C.c_int32), C.c_size_t, P(C.c_size_t)]),
+        "rtla_check_batch": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_int32, C.c_int32, P(C.c_int32),
+                                       P(C.c_uint64)]),
+        "rtla_check_replay": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_int32, C.c_int32, C.c_int,
+                                        P(C.c_int32), P(C.c_uint64)]),
+        "rtla_check_frontier": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(_AuditStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -145,7 +158,8 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_synthetic_generate", "rtla_synthetic_dedup", "rtla_orbit_key", "rtla_permute_row",
             "rtla_rows_text_hash", "rtla_level_text_hash", "rtla_row_layout", "rtla_rows_orbit_hash",
             "rtla_level_orbit_hash", "rtla_orbit_text", "rtla_probe_bench3", "rtla_random_texts",
-            "rtla_frontier_rows", "rtla_simulate", "rtla_sim_replay", "rtla_sim_walk"]
+            "rtla_frontier_rows", "rtla_simulate", "rtla_sim_replay", "rtla_sim_walk", "rtla_check_batch",
+            "rtla_check_replay", "rtla_check_frontier"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -291,6 +305,60 @@ def sim_walk(cfg: Config, start_row: Sequence[int], walk: int, depth: int, seed:
     rc = _check(_lib.rtla_sim_walk(C.byref(cc), arr, seed, walk, depth, rows, labels, cap, C.byref(n)), "rtla_sim_walk")
     return rc == VIOLATION, [(labels[k] & 0xFFFF, (labels[k] >> 16) & 0x7FFF, list(rows[k * w:(k + 1) * w]))
                              for k in range(n.value)]
+
+
+def inv_mask_of(invariants) -> int:
+    """RTLA_INV_* mask of invariant names (or a mask, passed through)."""
+    if isinstance(invariants, int):
+        return invariants
+    m = 0
+    for n in invariants:
+        m |= INV_BITS[n]
+    return m
+
+
+def inv_names(mask: int) -> List[str]:
+    """The names of a mask's invariants, in bit order."""
+    return [n for n, b in INV_BITS.items() if mask & b]
+
+
+@dataclass
+class AuditResult:
+    """One Checker.audit() call (rtla_audit_stats)."""
+    status: int = OK               # OK or VIOLATION
+    audited: int = 0               # rows of the frontier
+    evaluated: int = 0             # states evaluated: the rows, or (succ) their enabled successors
+    counts: dict = field(default_factory=dict)  # invariant name -> evaluated states that violate it
+    kernel_ms: float = 0.0
+    row_bytes: int = 0
+    violation: Optional[List[str]] = None  # the reported state's violated invariants, in bit order
+    viol_index: Optional[int] = None       # the least frontier index with a violation (as frontier() numbers rows)
+    viol_inst: int = -1                    # succ: the least violating action instance of that row
+    viol_mask: int = 0
+    viol_in_model: bool = True
+
+
+def _check_rows(fn, what: str, cfg: Config, rows, invariants, succ, *extra):
+    cc = cfg.c()
+    flat, n = _flat_rows(rows, row_words(cfg))
+    masks = (C.c_int32 * max(1, n))()
+    counts = (C.c_uint64 * 8)()
+    _check(fn(C.byref(cc), flat, n, inv_mask_of(invariants), int(succ), *extra, masks, counts), what)
+    return list(masks[:n]), {nm: counts[b.bit_length() - 1] for nm, b in INV_BITS.items()}
+
+
+def check_batch(cfg: Config, rows, invariants, succ: bool = False):
+    """Invariants evaluated outside the search, on the GPU (rtla_check_batch):
+    (masks, counts) -- masks[k] the violated mask of rows[k] (succ: the OR over
+    its enabled successors, evaluated as parent + delta), counts[name] the
+    evaluated states violating it.  `invariants` (names or a mask) is
+    independent of cfg.invariants."""
+    return _check_rows(_lib.rtla_check_batch, "rtla_check_batch", cfg, rows, invariants, succ)
+
+
+def check_replay(cfg: Config, rows, invariants, succ: bool = False, threads: int = 0):
+    """The same on the host (rtla_check_replay): no GPU, no context."""
+    return _check_rows(_lib.rtla_check_replay, "rtla_check_replay", cfg, rows, invariants, succ, threads)
 
 
 def _check(st: int, what: str):
@@ -670,6 +738,25 @@ class Checker:
         if rc < 0:
             raise RtlaError(rc, "rtla_simulate", st.flags)
         return _sim_result(rc, st, buf, n_walks)
+
+    def audit(self, invariants, succ: bool = False) -> AuditResult:
+        """Evaluate `invariants` (names or a mask; independent of the context's
+        own) over the states of the level last produced, in place on the GPU --
+        or, succ=True, over their enabled successors.  The BFS is left
+        untouched; after a VIOLATION result, violation() and trace() give the
+        counterexample (for succ, ending in the violating successor)."""
+        st = _AuditStats()
+        rc = _lib.rtla_check_frontier(self._h, inv_mask_of(invariants), int(succ), C.byref(st))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_check_frontier", st.flags)
+        res = AuditResult(status=rc, audited=st.audited, evaluated=st.evaluated, kernel_ms=st.kernel_ms,
+                          row_bytes=st.row_bytes,
+                          counts={nm: st.counts[b.bit_length() - 1] for nm, b in INV_BITS.items()})
+        if rc == VIOLATION:
+            res.violation = inv_names(st.viol_mask)
+            res.viol_index, res.viol_inst = st.viol_index, st.viol_inst
+            res.viol_mask, res.viol_in_model = st.viol_mask, bool(st.viol_in_model)
+        return res
 
     def coverage(self) -> dict:
         n = len(COVER_NAMES)

@@ -42,4 +42,15 @@ LogMatching == \A i, j \in Server :
                  \A n \in 1..(IF Len(log[i]) < Len(log[j]) THEN Len(log[i]) ELSE Len(log[j])) :
                     log[i][n].term = log[j][n].term =>
                         SubSeq(log[i], 1, n) = SubSeq(log[j], 1, n)
+
+\* State Machine Safety: no two servers hold different entries at an index both have committed.
+StateMachineSafety == \A i, j \in Server :
+    \A n \in 1..(IF commitIndex[i] < commitIndex[j] THEN commitIndex[i] ELSE commitIndex[j]) :
+        (n <= Len(log[i]) /\ n <= Len(log[j])) => log[i][n] = log[j][n]
+
+\* Current-state form: a leader holds every entry committed by a server whose term is not ahead of its own.
+LeaderCompleteness == \A i, j \in Server :
+    (state[i] = Leader /\ currentTerm[j] <= currentTerm[i]) =>
+        \A n \in 1..commitIndex[j] :
+            n <= Len(log[j]) => (n <= Len(log[i]) /\ log[i][n] = log[j][n])
 =====================================================================
