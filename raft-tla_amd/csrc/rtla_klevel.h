@@ -212,18 +212,81 @@ __device__ __noinline__ KeyStep key_one(const Layout& Lrt, const uint32_t* prow,
   return r;
 }
 
+// Entry k of a packed server / election record (at most PACKW words) for a
+// run-time k, as a select chain: a run-time index would move the record to scratch.
+__device__ __forceinline__ uint32_t pack_word(const uint32_t* a, int k) {
+  uint32_t v = a[0];
+#pragma unroll
+  for (int j = 1; j < PACKW; j++)
+    if (k == j) v = a[j];
+  return v;
+}
+// Word w of the successor row parent + d (ne: its election records): what
+// child_write (rtla_model.h) puts there, else the parent's word.  With a
+// compiled-in layout and a constant w every test but the compares against
+// d.srv, ne - 1 and the op slots folds away.
+template <class P, class R, int NR>
+__device__ __forceinline__ uint32_t child_word(const Layout& L, P prow, const DeltaT<NR>& d, const uint32_t* spk,
+                                               const uint32_t* epk, R all_new, FP fp, int ne, int w) {
+  if (w < 4)
+    return w == 0 ? (uint32_t)fp.a : w == 1 ? (uint32_t)(fp.a >> 32) : w == 2 ? (uint32_t)fp.b : (uint32_t)(fp.b >> 32);
+  if (w == L.off_hdr) return (uint32_t)d.nmsg | (uint32_t)ne << 8;
+  if (w >= L.off_all && w < L.off_elec) return all_new[w - L.off_all];
+  uint32_t v = prow[w];
+  if (w < L.off_all) {  // a server record
+    const int i = (w - L.off_srv) / L.srv_w;
+    if (d.srv == i) v = pack_word(spk, w - L.off_srv - i * L.srv_w);
+  } else if (w < L.off_bag) {  // an election record
+    const int e = (w - L.off_elec) / L.elec_w;
+    if (d.elec && e == ne - 1) v = pack_word(epk, w - L.off_elec - e * L.elec_w);
+  } else {  // a bag slot (or the padding word behind the bag: no op names it); a later op on a slot wins
+    const int q = (w - L.off_bag) / L.slot_w;
+    const bool hi = w - L.off_bag - q * L.slot_w != 0;
+#pragma unroll
+    for (int o = 0; o < 3; o++)
+      if (o < d.nops && d.op_slot[o] == q) v = hi ? (uint32_t)(d.op_new[o] >> 32) : (uint32_t)d.op_new[o];
+  }
+  return v;
+}
+// The successor row parent + d, assembled word by word by its own lane and
+// stored to dst (its W words; 4-byte aligned) with 16-byte stores: every
+// word written exactly once, by one lane, no copy of the parent row first.
+struct __attribute__((packed, aligned(4))) RowWords4 {
+  uint32_t v[4];
+};
+// (FIXED: a compiled-in layout -- the loop over the words unrolls in full.)
+template <bool FIXED, class P, class R, int NR>
+__device__ __forceinline__ void child_store(const Layout& L, P prow, const DeltaT<NR>& d, const uint32_t* spk,
+                                            const uint32_t* epk, R all_new, FP fp, uint32_t* dst) {
+  const int ne = row_nelec(L, prow) + (d.elec ? 1 : 0);
+  auto store4 = [&](int w) {
+    RowWords4 t;
+#pragma unroll
+    for (int k = 0; k < 4; k++) t.v[k] = child_word(L, prow, d, spk, epk, all_new, fp, ne, w + k);
+    *reinterpret_cast<RowWords4*>(dst + w) = t;
+  };
+  int w = 0;
+  if constexpr (FIXED) {
+#pragma unroll
+    for (; w + 4 <= L.W; w += 4) store4(w);
+#pragma unroll
+    for (; w < L.W; w++) dst[w] = child_word(L, prow, d, spk, epk, all_new, fp, ne, w);
+  } else {
+    for (; w + 4 <= L.W; w += 4) store4(w);
+    for (; w < L.W; w++) dst[w] = child_word(L, prow, d, spk, epk, all_new, fp, ne, w);
+  }
+}
+
 // One build_all lane as a function of its own (SYMMETRY kernels): the new
-// state's full Delta, fingerprint and invariants, then the words in which its
-// row differs from the parent's copy (child_write; `wait`: the copies must
-// land first).  NOT inlined for the same reason as key_one: at the SYMMETRY
+// state's full Delta, fingerprint and invariants, then its row (child_store;
+// dst = nullptr: none).  NOT inlined for the same reason as key_one: at the SYMMETRY
 // kernel's 128 VGPRs the inlined build pass is one of the two big spillers.
 struct BuildOut {
   int bad, sub, in_model;
 };
 template <int NS, Layout LC, int GROUP>
 __device__ __noinline__ BuildOut build_one(const Layout& Lrt, const uint32_t* prow, int inst, FP qfp,
-                                           const uint32_t* pall_p, uint32_t* d1, uint32_t* base2, int n1, int off,
-                                           bool write, bool wait) {
+                                           const uint32_t* pall_p, uint32_t* dst) {
   const Layout& L = pick_layout<LC>(Lrt);
   DeltaT<NS> d;
   d.enabled = 0;
@@ -232,13 +295,7 @@ __device__ __noinline__ BuildOut build_one(const Layout& Lrt, const uint32_t* pr
   BuildOut o{check_invariants_v<NS>(L, prow, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]), d.sub, d.in_model};
   uint32_t spk[PACKW], epk[PACKW];
   child_pack(L, d, spk, epk);
-  if (wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (write)
-    child_write(L, prow, d, spk, epk, StridedWords<GROUP>{const_cast<uint32_t*>(pall_p)}, cfp, [&](int w, uint32_t v) {
-      const int i = off + w;
-      if (i < n1) d1[i] = v;
-      else base2[i - n1] = v;
-    });
+  if (dst) child_store<LC.N != 0>(L, prow, d, spk, epk, StridedWords<GROUP>{const_cast<uint32_t*>(pall_p)}, cfp, dst);
   return o;
 }
 
@@ -341,14 +398,10 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   const int ninst = L.fam[F_COUNT];
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   // DuplicateMessage successors counted, not evaluated (see the group loop)
-  // (not in the narrow-row kernels at 4 waves/SIMD: the exhaust model's spills
-  // grow 39 -> 58 VGPRs with it and its run slows 1156 -> 1320 ms)
+  // (in the narrow-row kernels too since the round-6 pair ring: the exhaust
+  // model 1120-1127 against 1142-1150 ms, profiles/r09_rowbuild/others_ab.txt)
   constexpr bool narrow = !SYM && LC.N != 0 && LC.W <= RTLA_NARROW_W;
-  // (after the round-6 pair-ring changes, counting them there too measured
-  // 1122.3 vs 1145 ms on the exhaust model, profiles/r06_v6/fpset_ab.txt:
-  // found late and not adopted yet -- turning this on is a performance change)
-  constexpr bool dup_narrow = false;
-  const bool dup_counted = (!narrow || dup_narrow) && L.C == 1 && !(xflags & (XF_ALL_SUCCESSORS | XF_NO_CHUNKS));
+  const bool dup_counted = L.C == 1 && !(xflags & (XF_ALL_SUCCESSORS | XF_NO_CHUNKS));
   // Receive pairs are grouped by message type in the pair ring (4 ballots per
   // instance) only for SYMMETRY and max copies > 1 (round 6,
   // profiles/r06_v2/pairring_ab.txt: ungrouped configs[1] 178.1 vs 179.7 ms,
@@ -438,16 +491,21 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   // Build the rows of every pending new state (probes drained), one
   // next-level slot reservation for all of them (slots past next_cap are
   // dropped and flagged: the level is then reported incomplete):
-  //  (1) the wave copies each parent row (LDS) to its child's slot with
-  //      coalesced stores, for all of them (copying per batch of 64 instead,
-  //      so that the patches reach lines still in L2, was measured: no
-  //      fewer HBM writes, 5 % slower);
-  //  (2) per batch of 64, one state per lane: its full Delta (compute_delta
-  //      with slot bookkeeping; the probe pass only folded it into a hash),
-  //      fingerprint, invariants and distinct coverage -- the first batch's
-  //      arithmetic overlaps the copies in flight;
-  //  (3) after the copies landed (one wait), each lane stores the words in
-  //      which its child differs from the parent (child_write, rtla_model.h).
+  // per batch of 64, one state per lane:
+  //  (1) its full Delta (compute_delta with slot bookkeeping; the probe pass
+  //      only folded it into a hash), fingerprint, invariants and distinct
+  //      coverage;
+  //  (2) its row, assembled by the lane itself from the parent row in LDS
+  //      and the Delta (child_store) and stored with 16-byte stores; the
+  //      rows of a batch are contiguous, so its lines fill within the batch.
+  // Every word is stored once and nothing here waits for a store.
+  // The narrow-row kernels (rows of at most RTLA_NARROW_W words, 4 waves per
+  // SIMD: the exhaust model) keep the earlier form instead -- the wave copies
+  // every parent row to its child's slot with coalesced stores, waits for the
+  // copies, and each lane stores the words in which its child differs on top
+  // (child_write): with 21-word rows and few new states per group the copy is
+  // a handful of wave-wide steps, and the row per lane measured 1185-1225
+  // against 1142-1150 ms there (profiles/r09_rowbuild/others_ab.txt).
   // No separate row-building kernel: no parent-record read, no parent-row
   // gather, no second launch.
   auto build_all = [&]() {
@@ -464,7 +522,9 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     const unsigned long long p0 = ring_idx(next, obase);
     const int n1 = (int)min<unsigned long long>(next.cap - p0, (unsigned long long)nrows) * W;  // words before the wrap
     uint32_t* d1 = next.base + p0 * (unsigned long long)W;
-    // (1) for child rows [rb, re): word i of the run, lane-contiguous
+    // child c's row (a row never straddles the arena's end: n1 is whole rows)
+    auto row_at = [&](int c) { return c * W < n1 ? d1 + c * W : next.base + (c * W - n1); };
+    // narrow rows: for child rows [rb, re), word i of the run, lane-contiguous
     auto copy_rows = [&](int rb, int re) {
       const int nwords = re * W;
       int r = rb, w = lane;
@@ -481,8 +541,9 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
         while (w >= W) { w -= W; r++; }
       }
     };
-    if (rows_on) copy_rows(0, nrows);  // (all of them first: one pass of coalesced stores)
-    for (int b = 0; b < ntot; b += 64) {  // (2), (3)
+    if constexpr (narrow)
+      if (rows_on) copy_rows(0, nrows);  // (all of them first: one pass of coalesced stores)
+    for (int b = 0; b < ntot; b += 64) {
       const bool act = b + lane < ntot;
       const int e = act ? newl[(head + b + lane) & (NEWCAP - 1)] : 0;
       const int sl = e >> 8, inst = e & 255;
@@ -490,10 +551,8 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       if constexpr (SYM) {  // the lane's work as a call of its own (build_one)
         BuildOut o{0, 0, 0};
         if (act)
-          o = build_one<NS, LC, GROUP>(Lrt, rows + sl * W, inst, pfpl[sl], pall + sl, d1, next.base, n1, child * W,
-                                      rows_on && child < nrows, rows_on && b == 0);
-        else if (rows_on && b == 0)
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          o = build_one<NS, LC, GROUP>(Lrt, rows + sl * W, inst, pfpl[sl], pall + sl,
+                                      rows_on && child < nrows ? row_at(child) : nullptr);
         if (!(xflags & XF_ALL_SUCCESSORS) && claim_violation(ctr, o.bad, lane))
           record_violation(ctr, cur_base + s0 + sl, inst, 1, child < nrows ? next_base + obase + child : ~0ull);
         cover_add(cov + COVER_CODES, act, inst, o.sub);  // distinct coverage
@@ -521,18 +580,21 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       cover_add(cov + COVER_CODES, act, inst, d.sub);  // distinct coverage
       uint32_t spk[PACKW], epk[PACKW];  // the changed records, packed
       if (act) child_pack(L, d, spk, epk);
-      if (rows_on) {  // (3): the copies must land first (same words, other lanes)
-        if (b == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (child < nrows) {
-          const StridedWords<GROUP> pall_p{pall + sl};
-          const int off = child * W;
-          child_write(L, rows + sl * W, d, spk, epk, pall_p, cfp, [&](int w, uint32_t v) {
-            const int i = off + w;
-            if (i < n1) d1[i] = v;
-            else next.base[i - n1] = v;
-          });
+      if constexpr (narrow) {
+        if (rows_on) {  // the copies must land first (same words, other lanes)
+          if (b == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          if (child < nrows) {
+            const StridedWords<GROUP> pall_p{pall + sl};
+            const int off = child * W;
+            child_write(L, rows + sl * W, d, spk, epk, pall_p, cfp, [&](int w, uint32_t v) {
+              const int i = off + w;
+              if (i < n1) d1[i] = v;
+              else next.base[i - n1] = v;
+            });
+          }
         }
-      }
+      } else if (rows_on && child < nrows)  // (2)
+        child_store<LC.N != 0>(L, rows + sl * W, d, spk, epk, StridedWords<GROUP>{pall + sl}, cfp, row_at(child));
       if (child < nrows && RTLA_IDX_OK(ctr, next_base + obase + child, ctr->cap_parents))
         parents[next_base + obase + child] =
             (xflags & XF_ALL_SUCCESSORS)
@@ -847,6 +909,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
   if (MULTI) gnext = take_group();
   else if (lane == 0) gnext = atomicAdd(&ctr->group_next, 1ull);
   const unsigned long long ngroups = (s_end - s_begin + GROUP - 1) / GROUP;
+  [[maybe_unused]] uint32_t pfa_c = 0, pfb_c = 0;  // the group end's touches of the next tile's lines (below), carried to the next group
   for (unsigned long long gi = shfl0_u64(gnext); gi < ngroups; gi = shfl0_u64(gnext)) {
     if (!MULTI && lane == 0) gnext = atomicAdd(&ctr->group_next, 1ull);
     s0 = s_begin + gi * GROUP;
@@ -857,6 +920,8 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       // 16-byte aligned: s0 * W * 4 is a multiple of 128 * W, and the row tile's LDS offset of 16
       if (RTLA_IDX_OK(ctr, ring_idx(cur, s0) + nvalid, cur.cap + 1)) copy_words_lds16(rows, src, nw, lane);
     }
+    if constexpr (!narrow)  // (the previous group end's line touches: returned before this tile did)
+      asm volatile("" ::"v"(pfa_c), "v"(pfb_c));
     wave_sync();
     // the next group's number (its atomic returned before the tile copy's wait; MULTI: taken at the group's end)
     unsigned long long gnn = MULTI ? 0ull : shfl0_u64(gnext);
@@ -959,10 +1024,11 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     // tile load after this drain hits the caches.  Relaxed atomic loads: the
     // compiler issues them here (it does not sink an atomic) and tracks
     // their destination registers like any load (its vmcnt waits count
-    // them); the values are consumed only at the drain's end, so nothing
-    // waits for them before.  (an asm-issued load's register was
-    // invisible to the compiler.)
-    uint32_t pfa = 0, pfb = 0;
+    // them); the values are consumed only after the next group's tile load,
+    // so nothing waits for them before.  (an asm-issued load's
+    // register was invisible to the compiler.)
+    [[maybe_unused]] uint32_t pfa = 0, pfb = 0;  // (the narrow-row kernels': consumed at this group's end)
+    pfa_c = pfb_c = 0;
     if (MULTI) {
       gnext = take_group();
       gnn = shfl0_u64(gnext);
@@ -980,14 +1046,30 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       const int lines = ((int)min<unsigned long long>((unsigned long long)GROUP, s_end - sn) * W + 31) / 32;
       const uint32_t* pa = ring_row(cur, sn, W) + 32 * min(lane, lines - 1);
       const uint32_t* pb = ring_row(cur, sn, W) + 32 * min(lane + 64, lines - 1);
-      pfa = __hip_atomic_load(pa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      pfb = __hip_atomic_load(pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (narrow) {
+        pfa = __hip_atomic_load(pa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pfb = __hip_atomic_load(pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        pfa_c = __hip_atomic_load(pa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pfb_c = __hip_atomic_load(pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
     drain();
     if constexpr (!SYM) STAMP(7);  // (non-symmetric builds: slot 7 = the group-end probe drain alone)
     build_all();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("" ::"v"(pfa), "v"(pfb));
+    // No wait for the row and parent-record stores here (nothing reads them
+    // back in this launch; vmcnt counts stores too, so a wait for the two
+    // touches above would drain them all): the next group's tile load is
+    // issued behind them, and its own wait -- which it needs anyway -- is the
+    // first to cover them.  The tile may be overwritten: the row build read
+    // it from LDS into registers before storing, and LDS operations of a
+    // wave complete in order.  (The narrow-row kernels keep the wait and
+    // consume the touches here: carried over the loop they cost the
+    // 128-VGPR kernel 20-90 ms per exhaust-model run.)
+    if constexpr (narrow) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("" ::"v"(pfa), "v"(pfb));
+    }
     wave_sync();
     STAMP(6);  // group-end drain
   }

@@ -1224,9 +1224,12 @@ RTLA_HD FP alllogs_delta(const Layout& L, P row, Q all_out) {
 // calls; every other word of the child equals the parent's.  At most
 // 4 + 1 + srv_w + all_words + elec_w + 3 * slot_w words.  In two steps:
 // child_pack packs the delta's changed records (after which the wide
-// records are dead: the kernels pack before they wait for the parent-row
-// copies, and keep only the packed words across the wait), child_write
-// emits the words.
+// records are dead: the narrow-row level kernels, which copy the parent row
+// first, pack before they wait for the copies and keep only the packed
+// words across the wait), child_write emits the words.  The other level
+// kernels assemble the whole row from the packed records (child_word,
+// rtla_klevel.h: the same words, by word index); materialize below and those
+// narrow-row kernels are child_write's users.
 constexpr int PACKW = 6;  // words of a packed server / election record, at most (make_layout)
 template <int NR>
 RTLA_HD void child_pack(const Layout& L, const DeltaT<NR>& d, uint32_t* spk, uint32_t* epk) {
