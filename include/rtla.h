@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define RTLA_ABI_VERSION 10
+#define RTLA_ABI_VERSION 11
 
 /* status codes */
 #define RTLA_OK 0
@@ -354,7 +354,8 @@ int rtla_synthetic_generate(rtla_ctx *ctx, uint64_t seed, uint64_t first, uint64
 int rtla_synthetic_dedup(rtla_ctx *ctx, uint64_t begin, uint64_t end, rtla_level_stats *out);
 
 /* Calibration: n random 8-byte CAS inserts into a table of 2^log2 slots;
- * returns device seconds. */
+ * returns device seconds.  A key that hits the probe limit is not inserted:
+ * RTLA_E_OVERFLOW (rtla_probe_bench2 alike), *inserted still set. */
 int rtla_probe_bench(int log2, uint64_t n, double *seconds, uint64_t *inserted);
 /* n random keys inserted (CAS, all new), then re-probed (all present) with a
  * CAS and with the kernel's load-first protocol; device seconds of each pass. */
@@ -368,6 +369,24 @@ int rtla_probe_bench2(int log2, uint64_t n, double *s_insert, double *s_seen_cas
  * pass (HIP events); *inserted = keys it inserted. */
 int rtla_probe_bench3(int log2, uint64_t n_present, uint64_t n, double new_frac, double *seconds,
                       uint64_t *inserted);
+/* The kernels' fingerprint-set insert on caller-chosen fingerprints (no
+ * context; the tests' seam to the set).  fps: n (a, b) pairs; the key stored
+ * is b | 1, its home slot the top log2 bits of a (log2 in 10..30, else
+ * RTLA_E_ARG).  Input i is inserted by global thread i of 256-thread blocks
+ * (n <= 2^31), so the caller's order decides which inputs share a wavefront
+ * or a block.  protocol: 0 = one CAS per slot (Init, the wave-per-state
+ * kernel); 1 = CAS at the home slot, then CAS probing (the level kernel's
+ * pipelined probe); 2 = load the home slot, CAS only an empty slot (the level
+ * kernel's default probe); 3 = k_insert_remote itself, the exchange's owner
+ * side, on the inputs as one sender's region (its own thread mapping, several
+ * records per thread; a fingerprint 0:0 is a hole and never new).  table: 2^log2 u64,
+ * in/out -- uploaded before the launch, downloaded after it (all zero = an
+ * empty set), so a second call continues on the first call's table.
+ * is_new[i] = 1 if input i was inserted, 0 if it was found -- or dropped at
+ * the probe limit: then *flags has RTLA_CAP_FPSET and the call returns
+ * RTLA_E_OVERFLOW, every output filled all the same. */
+int rtla_fpset_probe(int log2, const uint64_t *fps, size_t n, int protocol, uint64_t *table, uint8_t *is_new,
+                     int32_t *flags);
 
 #ifdef __cplusplus
 }

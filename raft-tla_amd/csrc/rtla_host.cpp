@@ -160,8 +160,9 @@ static int alloc_shard(rtla_ctx* x, Shard& s, uint64_t budget) {
   const Layout& L = x->L;
   const int G = x->nshard;
   uint64_t tbytes = 8ull << x->tlog2;
-  // load factor <= 0.75 (RTLA_MODE_DEDUP: no BFS, no parent records)
-  s.parents_cap = x->cfg.mode == RTLA_MODE_DEDUP ? 64 : (1ull << x->tlog2) - (1ull << x->tlog2) / 4;
+  // One parent record per slot of the set (RTLA_MODE_DEDUP: no BFS, no parent records): a search that
+  // outgrows its set ends at the set's probe limit (RTLA_CAP_FPSET), whatever the load it reaches first.
+  s.parents_cap = x->cfg.mode == RTLA_MODE_DEDUP ? 64 : 1ull << x->tlog2;
   uint64_t pbytes = s.parents_cap * 8;
   uint64_t rowb = (uint64_t)L.W * 4;
   uint64_t boxb = G > 1 ? (uint64_t)G * x->box_cap * (16 + 8 + 4 + 16 + 4) +

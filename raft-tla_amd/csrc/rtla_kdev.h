@@ -210,6 +210,11 @@ __device__ __forceinline__ void cover_flush(const unsigned int* cov, int n, unsi
 
 // ---- the fingerprint set
 
+// The probe limit: an insert examines at most this many slots -- the home slot
+// and the ones after it, circularly -- before it gives up (FLAG_FPSET_FULL).
+// The same for the three protocols below, whichever way they count.
+constexpr int FPSET_PROBE_LIMIT = 4096;
+
 // Insert into the fingerprint set.  1 = newly inserted, 0 = already present,
 // -1 = probe limit exceeded (set too full).  Slots only ever change 0 -> key;
 // the CAS both tests and claims a slot, so every probe is one round trip.
@@ -217,7 +222,7 @@ __device__ __forceinline__ int fpset_insert(unsigned long long* table, int log2,
   const unsigned long long key = f.b | 1ull;
   const unsigned long long mask = (1ull << log2) - 1ull;
   unsigned long long idx = f.a >> (64 - log2);
-  for (int probe = 0; probe < 4096; probe++) {
+  for (int probe = 0; probe < FPSET_PROBE_LIMIT; probe++) {
     unsigned long long old = atomicCAS(&table[idx], 0ull, key);
     if (old == 0ull) return 1;
     if (old == key) return 0;
@@ -241,7 +246,7 @@ __device__ __forceinline__ bool fpset_resolve_loaded(unsigned long long* table, 
       if (seen == 0ull) return true;
       if (seen == key) return false;
     }
-    if (probe >= 4096) {
+    if (probe >= FPSET_PROBE_LIMIT) {
       set_flag(ctr, FLAG_FPSET_FULL);
       return false;
     }
@@ -256,7 +261,7 @@ __device__ __forceinline__ bool fpset_resolve(unsigned long long* table, int log
                                               unsigned long long idx, unsigned long long old, DevCounters* ctr) {
   const unsigned long long mask = (1ull << log2) - 1ull;
   for (int probe = 1; old != 0ull && old != key; probe++) {
-    if (probe >= 4096) {
+    if (probe >= FPSET_PROBE_LIMIT) {
       set_flag(ctr, FLAG_FPSET_FULL);
       return false;
     }

@@ -206,11 +206,41 @@ __global__ void k_probe_bench(unsigned long long* table, int tlog2, unsigned lon
       const unsigned long long v = __hip_atomic_load(&table[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       got += fpset_resolve_loaded(table, tlog2, f.b | 1ull, idx, v, ctr) ? 1 : 0;
     } else {
-      got += fpset_insert(table, tlog2, f) == 1;
+      const int r = fpset_insert(table, tlog2, f);
+      if (r < 0) set_flag(ctr, FLAG_FPSET_FULL);
+      got += r == 1;
     }
   }
   for (int off = 32; off > 0; off >>= 1) got += __shfl_down(got, off);
   if ((threadIdx.x & 63) == 0 && got) atomicAdd(&ctr->next_count, got);
+}
+
+// The three insert protocols of rtla_kdev.h on caller-chosen fingerprints
+// (rtla_fpset_probe): thread i inserts fps[i] -- no grid stride, so the
+// caller's order decides which inputs share a wave and which sit in different
+// blocks -- and writes whether it was new.  proto 0: fpset_insert (Init, the
+// wave kernel); 1: CAS at home, then fpset_resolve (the level kernel's
+// pipelined path, XF_CAS_ONLY); 2: load at home, then fpset_resolve_loaded
+// (the level kernel's default path, k_insert_remote, k_probe_mixed).
+__global__ void k_fpset_probe(unsigned long long* table, int tlog2, const unsigned long long* __restrict__ fps,
+                              unsigned long long n, int proto, unsigned char* __restrict__ is_new, DevCounters* ctr) {
+  const unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FP f{fps[2 * i], fps[2 * i + 1]};
+  const unsigned long long key = f.b | 1ull, idx = f.a >> (64 - tlog2);
+  bool isnew;
+  if (proto == 0) {
+    const int r = fpset_insert(table, tlog2, f);
+    if (r < 0) set_flag(ctr, FLAG_FPSET_FULL);
+    isnew = r == 1;
+  } else if (proto == 1) {
+    const unsigned long long old = atomicCAS(&table[idx], 0ull, key);
+    isnew = fpset_resolve(table, tlog2, key, idx, old, ctr);
+  } else {
+    const unsigned long long seen = __hip_atomic_load(&table[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    isnew = fpset_resolve_loaded(table, tlog2, key, idx, seen, ctr);
+  }
+  is_new[i] = isnew ? 1 : 0;
 }
 
 // Mixed-stream calibration (bench.py's random-access ceiling): probe i is,
@@ -387,6 +417,14 @@ hipError_t launch_probe_bench(uint64_t* table, int tlog2, uint64_t n, uint64_t s
                               hipStream_t st, int load_first) {
   hipLaunchKernelGGL(k_probe_bench, dim3(256 * 16), dim3(256), 0, st, (unsigned long long*)table, tlog2,
                      (unsigned long long)n, (unsigned long long)seed, ctr, load_first);
+  return hipGetLastError();
+}
+
+hipError_t launch_fpset_probe(uint64_t* table, int tlog2, const uint64_t* fps, uint64_t n, int proto,
+                              unsigned char* is_new, DevCounters* ctr, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_fpset_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (unsigned long long*)table,
+                     tlog2, (const unsigned long long*)fps, (unsigned long long)n, proto, is_new, ctr);
   return hipGetLastError();
 }
 

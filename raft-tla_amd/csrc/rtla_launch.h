@@ -123,5 +123,7 @@ hipError_t launch_probe_bench(uint64_t* table, int tlog2, uint64_t n, uint64_t s
                               DevCounters* ctr, hipStream_t st, int load_first = 0);
 hipError_t launch_probe_mixed(uint64_t* table, int tlog2, uint64_t n, uint64_t n_present, double new_frac,
                               uint64_t seed, DevCounters* ctr, hipStream_t st);
+hipError_t launch_fpset_probe(uint64_t* table, int tlog2, const uint64_t* fps, uint64_t n, int proto,
+                              unsigned char* is_new, DevCounters* ctr, hipStream_t st);
 
 }  // namespace rtla

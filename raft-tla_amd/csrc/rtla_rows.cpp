@@ -452,7 +452,7 @@ extern "C" int rtla_probe_bench(int log2, uint64_t n, double* seconds, uint64_t*
   DevCounters h;
   if (int rc = g.result(0, seconds, &h)) return rc;
   if (inserted) *inserted = h.next_count;
-  return RTLA_OK;
+  return h.flags & FLAG_FPSET_FULL ? RTLA_E_OVERFLOW : RTLA_OK;
 }
 
 // n random keys inserted (all new, CAS), then the same n keys probed again
@@ -476,7 +476,7 @@ extern "C" int rtla_probe_bench2(int log2, uint64_t n, double* s_insert, double*
   for (int k = 0; k < 3; k++)
     if (int rc = g.result(k, out[k], k == 2 ? &h : nullptr)) return rc;
   if (inserted) *inserted = h.next_count;  // the two re-probe passes insert nothing
-  return RTLA_OK;
+  return h.flags & FLAG_FPSET_FULL ? RTLA_E_OVERFLOW : RTLA_OK;
 }
 
 // n keys, a fraction new_frac of them new, probed into a table holding n_present keys: device seconds.
@@ -497,5 +497,58 @@ extern "C" int rtla_probe_bench3(int log2, uint64_t n_present, uint64_t n, doubl
   DevCounters h;
   if (int rc = g.result(0, seconds, &h)) return rc;
   if (inserted) *inserted = h.next_count;
+  return h.flags & FLAG_FPSET_FULL ? RTLA_E_OVERFLOW : RTLA_OK;
+}
+
+// The device insert functions on caller-chosen fingerprints (the tests' seam
+// to the fingerprint set): the table goes up, input i is inserted by global
+// thread i of k_fpset_probe -- or (protocol 3) the inputs by k_insert_remote
+// as the exchange launches it --, the table comes back.
+namespace {
+struct DevBuf {  // a device allocation released on every way out
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+}  // namespace
+
+extern "C" int rtla_fpset_probe(int log2, const uint64_t* fps, size_t n, int protocol, uint64_t* table,
+                                uint8_t* is_new, int32_t* flags) {
+  if (log2 < 10 || log2 > 30 || protocol < 0 || protocol > 3 || !table || !flags || n > (1ull << 31) ||
+      (n && (!fps || !is_new)))
+    return RTLA_E_ARG;
+  *flags = 0;
+  ProbeRig g(log2);
+  if (int rc = g.open(0)) return rc;
+  DevBuf d_fps, d_new;
+  HIPCHK(hipMalloc(&d_fps.p, std::max<size_t>(n, 1) * 16));
+  HIPCHK(hipMalloc(&d_new.p, std::max<size_t>(n, 1)));
+  HIPCHK(hipMemcpy(g.table, table, 8ull << log2, hipMemcpyHostToDevice));
+  if (n) HIPCHK(hipMemcpy(d_fps.p, fps, n * 16, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(d_new.p, 0, std::max<size_t>(n, 1)));
+  if (protocol == 3) {  // the exchange's owner side itself: the inputs as one sender's region of n records
+    DevBuf d_count, d_ans;
+    const uint64_t count = n;
+    HIPCHK(hipMalloc(&d_count.p, 8));
+    HIPCHK(hipMalloc(&d_ans.p, std::max<size_t>(n, 1) * 4));
+    HIPCHK(hipMemcpy(d_count.p, &count, 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_ans.p, 0, std::max<size_t>(n, 1) * 4));
+    HIPCHK(launch_insert_remote((const uint64_t*)d_fps.p, (const uint64_t*)d_count.p, 1, n, g.table, log2,
+                                (uint32_t*)d_ans.p, g.ctr, n, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<uint32_t> ans(n);
+    if (n) HIPCHK(hipMemcpy(ans.data(), d_ans.p, n * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n; k++) is_new[k] = ans[k] ? 1 : 0;
+  } else {
+    HIPCHK(launch_fpset_probe(g.table, log2, (const uint64_t*)d_fps.p, n, protocol, (unsigned char*)d_new.p, g.ctr,
+                              nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (n) HIPCHK(hipMemcpy(is_new, d_new.p, n, hipMemcpyDeviceToHost));
+  }
+  DevCounters h;
+  HIPCHK(hipMemcpy(&h, g.ctr, sizeof h, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(table, g.table, 8ull << log2, hipMemcpyDeviceToHost));
+  *flags = h.flags;
   return h.flags & FLAG_FPSET_FULL ? RTLA_E_OVERFLOW : RTLA_OK;
 }

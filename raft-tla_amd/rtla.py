@@ -140,6 +140,8 @@ def _load():
         "rtla_check_replay": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_int32, C.c_int32, C.c_int,
                                         P(C.c_int32), P(C.c_uint64)]),
         "rtla_check_frontier": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(_AuditStats)]),
+        "rtla_fpset_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                       P(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -159,7 +161,7 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_rows_text_hash", "rtla_level_text_hash", "rtla_row_layout", "rtla_rows_orbit_hash",
             "rtla_level_orbit_hash", "rtla_orbit_text", "rtla_probe_bench3", "rtla_random_texts",
             "rtla_frontier_rows", "rtla_simulate", "rtla_sim_replay", "rtla_sim_walk", "rtla_check_batch",
-            "rtla_check_replay", "rtla_check_frontier"]
+            "rtla_check_replay", "rtla_check_frontier", "rtla_fpset_probe"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -806,3 +808,35 @@ def probe_bench(log2: int, n: int):
     s, ins = C.c_double(0), C.c_uint64(0)
     _check(_lib.rtla_probe_bench(log2, n, C.byref(s), C.byref(ins)), "rtla_probe_bench")
     return s.value, ins.value
+
+
+FPSET_INSERT, FPSET_CAS_RESOLVE, FPSET_LOAD_RESOLVE, FPSET_REMOTE = 0, 1, 2, 3  # rtla_fpset_probe's protocols
+
+
+def fpset_probe_status(log2: int, fps, protocol: int, table=None):
+    """rtla_fpset_probe as it is: (status, new, table, flags) -- fps an (n, 2)
+    numpy u64 array of (a, b) pairs, table 2^log2 u64 (None = empty; left
+    unchanged).  Raises only where the call filled no output."""
+    import numpy as np
+    fps = np.ascontiguousarray(fps, dtype=np.uint64).reshape(-1, 2)
+    valid = 10 <= log2 <= 30  # (else the call refuses, and touches no buffer)
+    out = np.zeros(1 << log2 if valid else 1, np.uint64) if table is None else np.array(table, dtype=np.uint64)
+    if valid and out.shape != (1 << log2,):
+        raise ValueError("table must hold 2^log2 u64")
+    new = np.zeros(len(fps), np.uint8)
+    flags = C.c_int32(0)
+    rc = _lib.rtla_fpset_probe(log2, fps.ctypes.data, len(fps), protocol, out.ctypes.data, new.ctypes.data,
+                               C.byref(flags))
+    if rc < 0 and rc != E_OVERFLOW:
+        raise RtlaError(rc, "rtla_fpset_probe", flags.value)
+    return rc, new, out, flags.value
+
+
+def fpset_probe(log2: int, fps, protocol: int, table=None):
+    """The kernels' fingerprint-set insert on chosen fingerprints
+    (rtla_fpset_probe): input i is inserted by global thread i with protocol
+    0 (fpset_insert), 1 (home CAS + fpset_resolve) or 2 (home load +
+    fpset_resolve_loaded); 3 runs k_insert_remote on the inputs.  Returns (new, table, flags): one byte per input,
+    the table afterwards, RTLA_CAP_FPSET in flags when an insert hit the probe
+    limit (the outputs are complete either way)."""
+    return fpset_probe_status(log2, fps, protocol, table)[1:]
