@@ -42,6 +42,11 @@
  *                            another INVARIANT list: any invariant set evaluated
  *                            outside the search, over the states of the level
  *                            last produced (in place in HBM) or a batch of rows.
+ *   rtla_pred_compile,
+ *   rtla_pred_frontier ...   an operator added to MC.tla and named under
+ *                            INVARIANT: a predicate in a TLA+ subset over the
+ *                            spec's variables, compiled to a bounded bytecode
+ *                            and evaluated by one interpreter on host and GPU.
  *   rtla_sim_replay,
  *   rtla_sim_walk            the same walks recomputed on the host from
  *                            (seed, walk id): reproduce one behaviour, as TLC
@@ -321,6 +326,41 @@ typedef struct {
  * the violating successor after it) until the next rtla_check_frontier,
  * rtla_simulate, rtla_step or rtla_reset. */
 int rtla_check_frontier(rtla_ctx *ctx, int32_t inv_mask, int32_t succ, rtla_audit_stats *out);
+
+/* User-defined state predicates (TLC: an operator added to MC.tla and named
+ * under INVARIANT).  `text` holds up to 8 definitions `Name == expr` in the
+ * predicate language, a TLA+ subset over the spec's variables (grammar,
+ * bytecode and the termination bound: DESIGN.md section 13; the built-ins
+ * restated in it: specs/MCPredicates.tla); definition k is bit k of every mask
+ * and counts[k] below -- definition bits, not RTLA_INV_*.  A mask holds the
+ * definitions that are FALSE on a state.
+ * rtla_pred_compile: RTLA_E_CONFIG for a cfg outside the row format;
+ * RTLA_E_ARG with "line:col: message" in err for a syntax, type or bound error
+ * (more than 8 definitions, 6 bound variables, 512 program words, operand depth
+ * 16 or 2^20 worst-case steps per row).  A compiled set is bound to the row
+ * layout of its cfg: used with another, RTLA_E_ARG.
+ * An evaluation error (log[i][n] with n outside 1..Len(log[i]), a per-type
+ * message field read on a message of another type, a function applied to Nil)
+ * fails the call: RTLA_E_SPEC (RTLA_CAP_SPEC_ERROR), on host and device alike.
+ * rtla_pred_replay evaluates on the host (threads as rtla_check_replay),
+ * rtla_pred_batch on the GPU, stateless (test-sized inputs); counts may be NULL
+ * (8 u64).  rtla_pred_frontier evaluates over the context's current frontier in
+ * place, with rtla_check_frontier's preconditions, touching nothing of the
+ * search (states only: no successor mode); out->viol_mask and out->counts index
+ * definitions.  After RTLA_VIOLATION, rtla_violation (inv_mask = definition
+ * bits, in_model = 1) and rtla_trace report the BFS parent chain from Init to
+ * the least false row until the next rtla_pred_frontier, rtla_check_frontier,
+ * rtla_simulate, rtla_step or rtla_reset. */
+typedef struct rtla_pred rtla_pred;
+int rtla_pred_compile(const rtla_cfg *cfg, const char *text, rtla_pred **out, char *err, size_t errcap);
+void rtla_pred_free(rtla_pred *p);
+int rtla_pred_count(const rtla_pred *p);
+int rtla_pred_name(const rtla_pred *p, int k, char *buf, size_t cap);
+int rtla_pred_replay(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *rows, size_t n, int threads,
+                     int32_t *masks, uint64_t *counts);
+int rtla_pred_batch(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *rows, size_t n, int32_t *masks,
+                    uint64_t *counts);
+int rtla_pred_frontier(rtla_ctx *ctx, const rtla_pred *p, rtla_audit_stats *out);
 
 /* Diagnostic (performance analysis only): re-expand the current frontier
  * `reps` times with the level kernel's experiment switches `xflags` (XF_*

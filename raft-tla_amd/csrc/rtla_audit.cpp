@@ -13,7 +13,7 @@ static bool audit_args_ok(int32_t inv_mask, int32_t succ) {
   return inv_mask >= 0 && inv_mask <= INV_ALL && (succ == 0 || succ == 1);
 }
 
-static AuditCounters audit_zero() {
+AuditCounters audit_zero() {
   AuditCounters h;
   memset(&h, 0, sizeof h);
   h.viol_key = AUDIT_NO_VIOLATION;
@@ -60,11 +60,8 @@ extern "C" int rtla_check_replay(const rtla_cfg* c, const uint32_t* rows, size_t
 
 // Stateless, like rtla_expand_batch: the rows are staged into a device buffer
 // of their own (test-sized inputs).
-extern "C" int rtla_check_batch(const rtla_cfg* c, const uint32_t* rows, size_t n, int32_t inv_mask, int32_t succ,
-                                int32_t* masks, uint64_t* counts) {
-  CFG_LAYOUT(L, c);
-  if (!audit_args_ok(inv_mask, succ) || !masks || (n && !rows)) return RTLA_E_ARG;
-  L.inv_mask = inv_mask;
+int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaunch& launch, int32_t* masks,
+                uint64_t* counts) {
   const uint64_t cap = round64(std::max<size_t>(n, 1));
   uint32_t* d_rows = nullptr;
   int* d_masks = nullptr;
@@ -76,7 +73,7 @@ extern "C" int rtla_check_batch(const rtla_cfg* c, const uint32_t* rows, size_t 
     HIPCHK(hipMalloc(&d_ctr, sizeof h));
     HIPCHK(hipMemcpy(d_rows, rows, n * (size_t)L.W * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_ctr, &h, sizeof h, hipMemcpyHostToDevice));
-    HIPCHK(launch_audit(L, Ring{d_rows, 0, cap}, n, succ, d_masks, d_ctr, nullptr));
+    HIPCHK(launch(Ring{d_rows, 0, cap}, n, d_masks, d_ctr, nullptr));
     HIPCHK(hipMemcpy(&h, d_ctr, sizeof h, hipMemcpyDeviceToHost));
     if (n) HIPCHK(hipMemcpy(masks, d_masks, n * sizeof(int), hipMemcpyDeviceToHost));
     return RTLA_OK;
@@ -93,14 +90,20 @@ extern "C" int rtla_check_batch(const rtla_cfg* c, const uint32_t* rows, size_t 
   return RTLA_OK;
 }
 
-extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, rtla_audit_stats* out) {
-  if (!x) return RTLA_E_ARG;
+extern "C" int rtla_check_batch(const rtla_cfg* c, const uint32_t* rows, size_t n, int32_t inv_mask, int32_t succ,
+                                int32_t* masks, uint64_t* counts) {
+  CFG_LAYOUT(L, c);
+  if (!audit_args_ok(inv_mask, succ) || !masks || (n && !rows)) return RTLA_E_ARG;
+  L.inv_mask = inv_mask;
+  return audit_batch(L, rows, n, [&](const Ring& cur, uint64_t nr, int* m, AuditCounters* ctr, hipStream_t st) {
+    return launch_audit(L, cur, nr, succ, m, ctr, st);
+  }, masks, counts);
+}
+
+int audit_frontier(rtla_ctx* x, int succ, bool pred, const AuditLaunch& launch, rtla_audit_stats* out) {
   if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
       x->sh[0].n_cur == 0)
     return RTLA_E_STATE;
-  if (!audit_args_ok(inv_mask, succ)) return RTLA_E_ARG;
-  Layout L = x->L;
-  L.inv_mask = inv_mask;
   HIPCHK(hipSetDevice(x->device));
   Shard& s = x->sh[0];
   AuditState& a = x->audit;
@@ -112,7 +115,7 @@ extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, 
   AuditCounters h = audit_zero();
   HIPCHK(hipMemcpyAsync(a.ctr, &h, sizeof h, hipMemcpyHostToDevice, x->stream));
   HIPCHK(hipEventRecord(a.ev0, x->stream));
-  HIPCHK(launch_audit(L, cur_ring(x, s), s.n_cur, succ, nullptr, a.ctr, x->stream));
+  HIPCHK(launch(cur_ring(x, s), s.n_cur, nullptr, a.ctr, x->stream));
   HIPCHK(hipEventRecord(a.ev1, x->stream));
   HIPCHK(hipMemcpyAsync(&h, a.ctr, sizeof h, hipMemcpyDeviceToHost, x->stream));
   HIPCHK(hipStreamSynchronize(x->stream));
@@ -127,8 +130,8 @@ extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, 
     a.viol = true;
     a.start = s.cur_base + audit_key_index(h.viol_key);
     a.inst = succ ? audit_key_inst(h.viol_key) : -1;
-    a.mask = audit_key_mask(h.viol_key);
-    a.in_model = audit_key_in_model(h.viol_key);
+    a.mask = pred ? pred_key_mask(h.viol_key) : audit_key_mask(h.viol_key);
+    a.in_model = pred ? 1 : audit_key_in_model(h.viol_key);
   }
   if (out) {
     memset(out, 0, sizeof *out);
@@ -137,7 +140,7 @@ extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, 
     static_assert(sizeof out->counts / sizeof out->counts[0] == AUDIT_COUNTS, "rtla_audit_stats.counts");
     audit_counts_out(h, out->counts);
     out->kernel_ms = ms;
-    out->row_bytes = (uint64_t)L.W * 4;
+    out->row_bytes = (uint64_t)x->L.W * 4;
     out->viol_index = ~0ull;
     out->viol_inst = -1;
     if (a.viol) {
@@ -150,4 +153,17 @@ extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, 
     out->flags = h.flags;
   }
   return status;
+}
+
+extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, rtla_audit_stats* out) {
+  if (!x) return RTLA_E_ARG;
+  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
+      x->sh[0].n_cur == 0)
+    return RTLA_E_STATE;
+  if (!audit_args_ok(inv_mask, succ)) return RTLA_E_ARG;
+  Layout L = x->L;
+  L.inv_mask = inv_mask;
+  return audit_frontier(x, succ, false, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
+    return launch_audit(L, cur, n, succ, m, ctr, st);
+  }, out);
 }

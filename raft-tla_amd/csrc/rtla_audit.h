@@ -31,6 +31,10 @@ RTLA_HD uint64_t audit_key_index(uint64_t key) { return key >> 24; }
 RTLA_HD int audit_key_inst(uint64_t key) { return (int)(key >> 8 & 0xffff); }
 RTLA_HD int audit_key_in_model(uint64_t key) { return (int)(key >> 5 & 1); }
 RTLA_HD int audit_key_mask(uint64_t key) { return (int)(key & INV_ALL); }
+// The key of a predicate audit (rtla_kpred.hip; rows only, no instance): the low
+// eight bits are the row's false definitions (rtla_audit_stats.counts has eight).
+RTLA_HD uint64_t pred_key(uint64_t index, int mask) { return index << 24 | (uint64_t)(mask & 255); }
+RTLA_HD int pred_key_mask(uint64_t key) { return (int)(key & 255); }
 
 // Device counters of one audit launch (the host's tally has the same shape).
 struct AuditCounters {

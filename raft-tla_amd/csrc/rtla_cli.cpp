@@ -16,6 +16,11 @@
 // starts at state w mod |level K|).  Walk ids are global: processes given
 // disjoint [F, F + N) ranges and the same seed explore disjoint walks, so a
 // large simulation can be split over GPUs by hand (-gpus > 1 is refused).
+// TLC's "add an operator to MC.tla and name it under INVARIANT" is
+//     rtla -predicates FILE -config X.cfg SPEC.tla
+// a name under INVARIANT(S) or -audit that is not built in is looked up in FILE
+// (the predicate language of DESIGN.md section 13), compiled, and checked on
+// every level of the search right after it is produced (-gpus 1 only).
 //
 // SPEC.tla is either the reference's raft.tla (sha256 checked: the semantics
 // are compiled into the kernels, not parsed) or a wrapper module that
@@ -29,6 +34,7 @@
 // 12 = safety violation, 150/151 = spec/config errors, 255 = other errors
 // (TLC's ExitStatus values as we understand them; not verified against a
 // live TLC here).
+#include <ctype.h>
 #include <errno.h>
 #include <signal.h>
 #include <spawn.h>
@@ -40,6 +46,7 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <filesystem>
 #include <fstream>
@@ -210,11 +217,13 @@ void usage() {
           "            [-raft PATH/raft.tla] [-skip-spec-check]\n"
           "            [-checkpoint MINUTES] [-checkpointdir PREFIX] [-recover PREFIX]\n"
           "            [-simulate [num=N[,first=F]]] [-depth D] [-seed S] [-bfs-levels K]\n"
-          "            [-audit Name[,Name...]]\n"
+          "            [-audit Name[,Name...]] [-predicates FILE]\n"
           "            -config FILE.cfg SPEC.tla\n"
           "  -simulate: after K BFS levels (default 1 = Init only) run N random walks (default 1000000) of up to\n"
           "  D steps (default 100) from the states of level K; walk ids F .. F+N-1 are global, so runs with\n"
           "  disjoint ranges and the same seed compose; one GPU only.\n"
+          "  -predicates FILE: definitions in the predicate language (specs/MCPredicates.tla) that INVARIANT(S) and\n"
+          "          -audit may name beside the built-in invariants; checked on every level of the search (-gpus 1)\n"
           "  -audit: when the BFS stops (exhausted, out of capacity, or after -bfs-levels K) evaluate the named\n"
           "  invariants -- any of the specification's, not only the cfg's -- over the states of the last level;\n"
           "  one GPU only.\n");
@@ -356,6 +365,86 @@ int32_t invariant_bit(const std::string& name) {
   return 0;
 }
 
+// ---- -predicates FILE: user-defined invariants
+
+// `text` with every definition whose name is not in `keep` blanked out (line breaks kept, so a compile error's
+// line:col is the file's): the set compiled is the set named, and only it is evaluated.  A definition starts at
+// an identifier followed by `==` outside comments and ends where the next one, or the module's closing line, starts.
+std::string select_definitions(const std::string& text, const std::vector<std::string>& keep) {
+  struct Def { size_t at; std::string name; };
+  std::vector<Def> defs;
+  size_t end = text.size();
+  for (size_t i = 0; i < text.size();) {
+    if (text.compare(i, 2, "\\*") == 0) {
+      while (i < text.size() && text[i] != '\n') i++;
+    } else if (text.compare(i, 2, "(*") == 0) {
+      int deep = 0;
+      do {
+        if (text.compare(i, 2, "(*") == 0) { deep++; i += 2; }
+        else if (text.compare(i, 2, "*)") == 0) { deep--; i += 2; }
+        else i++;
+      } while (deep > 0 && i < text.size());
+    } else if (text.compare(i, 4, "====") == 0) {
+      end = i;
+      break;
+    } else if (isalpha((unsigned char)text[i]) || text[i] == '_') {
+      size_t j = i;
+      while (j < text.size() && (isalnum((unsigned char)text[j]) || text[j] == '_')) j++;
+      size_t k = j;
+      while (k < text.size() && (text[k] == ' ' || text[k] == '\t')) k++;
+      if (text.compare(k, 2, "==") == 0 && text.compare(k, 3, "===") != 0) defs.push_back({i, text.substr(i, j - i)});
+      i = j;
+    } else {
+      i++;
+    }
+  }
+  std::string out = text;
+  for (size_t d = 0; d < defs.size(); d++) {
+    if (std::find(keep.begin(), keep.end(), defs[d].name) != keep.end()) continue;
+    const size_t stop = d + 1 < defs.size() ? defs[d + 1].at : end;
+    for (size_t i = defs[d].at; i < stop; i++)
+      if (out[i] != '\n') out[i] = ' ';
+  }
+  return out;
+}
+
+// The definitions `names` of the predicate file, compiled for *c; exits as for an undefined invariant.
+rtla_pred* load_predicates(const rtla_cfg* c, const std::string& path, const std::vector<std::string>& names) {
+  std::ifstream in(path);
+  if (!in) { printf("Error: cannot read the predicate file %s\n", path.c_str()); exit(150); }
+  std::stringstream ss;
+  ss << in.rdbuf();
+  char err[512];
+  rtla_pred* all = nullptr;
+  if (rtla_pred_compile(c, ss.str().c_str(), &all, err, sizeof err) != RTLA_OK) {
+    printf("Error: %s:%s\n", path.c_str(), err[0] ? err : " the configuration is outside the row format");
+    exit(150);
+  }
+  for (auto& nm : names) {
+    bool found = false;
+    char buf[256];
+    for (int k = 0; k < rtla_pred_count(all); k++)
+      found |= rtla_pred_name(all, k, buf, sizeof buf) >= 0 && nm == buf;
+    if (!found) {
+      printf("Error: The invariant %s specified in the configuration file is not defined in the specification.\n",
+             nm.c_str());
+      exit(150);
+    }
+  }
+  rtla_pred_free(all);
+  rtla_pred* set = nullptr;
+  if (rtla_pred_compile(c, select_definitions(ss.str(), names).c_str(), &set, err, sizeof err) != RTLA_OK) {
+    printf("Error: %s:%s\n", path.c_str(), err);
+    exit(150);
+  }
+  return set;
+}
+std::string pred_name(const rtla_pred* p, int k) {
+  char buf[256] = "";
+  rtla_pred_name(p, k, buf, sizeof buf);
+  return buf;
+}
+
 const char* COVER[] = {"Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientRequest",
                        "AdvanceCommitIndex", "AppendEntries", "Receive", "DuplicateMessage", "DropMessage",
                        "UpdateTerm", "HandleRequestVoteRequest", "HandleRequestVoteResponse",
@@ -380,6 +469,8 @@ int main(int argc, char** argv) {
   // -audit Name[,Name...]: invariants evaluated over the last BFS level
   bool audit = false;
   std::vector<std::string> audit_names;
+  // -predicates FILE: definitions that INVARIANT(S) and -audit may name beside the built-in ones
+  std::string pred_file;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -418,6 +509,7 @@ int main(int argc, char** argv) {
       for (std::string nm; std::getline(names, nm, ',');)
         if (!nm.empty()) audit_names.push_back(nm);
     }
+    else if (a == "-predicates") pred_file = next();
     else if (a == "-h" || a == "-help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { fprintf(stderr, "Error: unsupported option %s\n", a.c_str()); return 255; }
     else spec = a;
@@ -431,6 +523,10 @@ int main(int argc, char** argv) {
   }
   if (audit && (gpus > 1 || simulate || audit_names.empty())) {
     fprintf(stderr, "Error: -audit names at least one invariant and runs on one GPU, without -simulate\n");
+    return 255;
+  }
+  if (!pred_file.empty() && gpus > 1) {
+    fprintf(stderr, "Error: -predicates checks user-defined invariants on one GPU (a single shard); use -gpus 1\n");
     return 255;
   }
   if (audit && bfs_levels < 1) {
@@ -506,7 +602,9 @@ int main(int argc, char** argv) {
   };
   rtla_cfg c;
   memset(&c, 0, sizeof c);
+  std::vector<std::string> user_invs, user_audit;  // names to look up in the predicate file
   for (auto& inv : cf.invariants) {
+    if (!pred_file.empty() && !defined(inv)) { user_invs.push_back(inv); continue; }
     if (!defined(inv) || inv == "StateConstraint") {
       printf("Error: The invariant %s specified in the configuration file is not defined in the specification.\n",
              inv.c_str());
@@ -516,6 +614,7 @@ int main(int argc, char** argv) {
   }
   int32_t audit_mask = 0;
   for (auto& inv : audit_names) {
+    if (!pred_file.empty() && !defined(inv)) { user_audit.push_back(inv); continue; }
     if (!defined(inv) || inv == "StateConstraint") {
       printf("Error: The invariant %s specified in the configuration file is not defined in the specification.\n",
              inv.c_str());
@@ -575,6 +674,17 @@ int main(int argc, char** argv) {
       return 151;
     }
   }
+  rtla_pred* preds = user_invs.empty() ? nullptr : load_predicates(&c, pred_file, user_invs);
+  rtla_pred* audit_preds = user_audit.empty() ? nullptr : load_predicates(&c, pred_file, user_audit);
+  bool pred_violation = false;  // the violation reported is a predicate set's: its mask holds definition bits
+  const rtla_pred* viol_set = nullptr;
+  // user-defined invariants: the level just produced is audited in place (rtla_pred_frontier)
+  auto check_level = [&](rtla_ctx* x, int st_level, uint64_t new_states) -> int {
+    if (!preds || st_level != RTLA_OK || new_states == 0) return st_level;
+    const int rc = rtla_pred_frontier(x, preds, nullptr);
+    if (rc == RTLA_VIOLATION) { pred_violation = true; viol_set = preds; }
+    return rc == RTLA_OK ? st_level : rc;
+  };
   unsigned char comm_id[128];
   if (world > 1 && !rendezvous(rank, getenv("RTLA_RENDEZVOUS"), false, comm_id)) {
     fprintf(stderr, "Error: rank %d: RCCL rendezvous failed\n", rank);
@@ -599,6 +709,7 @@ int main(int argc, char** argv) {
   } else {
     st = rtla_init(ctx, &ls);
     printf("Finished computing initial states: 1 distinct state generated at %s.\n", now_str().c_str());
+    st = check_level(ctx, st, 1);
   }
   auto last_progress = t0, last_ckpt = t0;
   // With several ranks the checkpoint (a collective) must be decided alike
@@ -609,6 +720,8 @@ int main(int argc, char** argv) {
   const bool stop_at_level = simulate || (audit && have_levels);
   while (st == RTLA_OK && !(stop_at_level && ls.level >= bfs_levels)) {
     st = rtla_step(ctx, &ls);
+    if (st < 0) break;
+    st = check_level(ctx, st, ls.new_states);
     if (st < 0) break;
     dev_s += ls.kernel_ms / 1e3;
     const double since = world > 1 ? dev_s - dev_ckpt
@@ -676,6 +789,30 @@ int main(int argc, char** argv) {
                                  (unsigned long long)as.counts[b], (unsigned long long)as.audited);
         else printf("Invariant %s holds in all %llu states.\n", INVARIANTS[b].name, (unsigned long long)as.audited);
       }
+    if (audit_preds) {  // the names the predicate file defines, in the same form
+      rtla_audit_stats ps;
+      memset(&ps, 0, sizeof ps);
+      const int pst = rtla_pred_frontier(ctx, audit_preds, &ps);
+      if (pst < 0) {
+        printf("Error: audit: %s\n", rtla_strerror(pst));
+        rtla_close(ctx);
+        return 255;
+      }
+      for (int k = 0; k < rtla_pred_count(audit_preds); k++) {
+        if (ps.counts[k]) printf("Error: Invariant %s is violated by %llu of the %llu states.\n",
+                                 pred_name(audit_preds, k).c_str(), (unsigned long long)ps.counts[k],
+                                 (unsigned long long)ps.audited);
+        else printf("Invariant %s holds in all %llu states.\n", pred_name(audit_preds, k).c_str(),
+                    (unsigned long long)ps.audited);
+      }
+      if (pst == RTLA_VIOLATION) {
+        st = pst;
+        pred_violation = true;
+        viol_set = audit_preds;
+      } else if (st == RTLA_VIOLATION) {  // (the trace reported is the last audit's: the built-ins' again)
+        st = rtla_check_frontier(ctx, audit_mask, 0, &as);
+      }
+    }
     secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   } else if (audit && st == RTLA_DONE) {
     printf("Audit: the search is complete and its last level is empty; nothing to audit.\n");
@@ -717,8 +854,13 @@ int main(int argc, char** argv) {
   if (st == RTLA_VIOLATION) {
     int32_t mask = 0, inm = 0;
     rtla_violation(ctx, &mask, &inm);
-    for (auto& i : INVARIANTS)  // every violated name, in bit order
-      if (mask & i.bit) printf("Error: Invariant %s is violated.\n", i.name);
+    if (pred_violation) {
+      for (int k = 0; k < rtla_pred_count(viol_set); k++)  // every false definition of the state, in file order
+        if (mask >> k & 1) printf("Error: Invariant %s is violated.\n", pred_name(viol_set, k).c_str());
+    } else {
+      for (auto& i : INVARIANTS)  // every violated name, in bit order
+        if (mask & i.bit) printf("Error: Invariant %s is violated.\n", i.name);
+    }
     printf("Error: The behavior up to this point is:\n");
     size_t n = 0;
     rtla_trace(ctx, nullptr, nullptr, 0, &n);

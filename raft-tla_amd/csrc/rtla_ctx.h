@@ -4,6 +4,7 @@
 //   rtla_ckpt.cpp     checkpoint / recover
 //   rtla_simhost.cpp  random-walk simulation
 //   rtla_audit.cpp    invariants outside the search: batch, host replay, frontier audit
+//   rtla_predhost.cpp user-defined predicates: the rtla_pred_* ABI over the compiler (rtla_pred.cpp) and the audit
 //   rtla_rows.cpp     the context-free row API, synthetic and probe micro-benchmarks
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <functional>
 #include <type_traits>
 #include <vector>
 
@@ -81,6 +83,7 @@ struct SimState {
 // and the violation its last call found (rtla_violation / rtla_trace).
 struct AuditState {
   AuditCounters* ctr = nullptr;
+  uint32_t* prog = nullptr;  // rtla_pred_frontier: the program's device copy (PRED_MAX_WORDS words)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool viol = false;
   uint64_t start = 0;  // parent-record index of the violating row (succ: of the violating successor's parent)
@@ -191,6 +194,14 @@ int env_xflags();
 int layout_from_cfg(const rtla_cfg* c, Layout* L);
 bool fault_here(const rtla_ctx* x, const char* where);
 void print_stamps(const DevCounters& c, int level);
+// rtla_audit.cpp: one audit launch (`launch`: the kernel, over the ring, row count, device counters and stream it
+// is given) over host rows staged into a device buffer / over the context's frontier where it lies.  pred: the
+// masks are a predicate set's definition bits (pred_key), not RTLA_INV_*.
+using AuditLaunch = std::function<hipError_t(const Ring&, uint64_t, int*, AuditCounters*, hipStream_t)>;
+AuditCounters audit_zero();
+int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaunch& launch, int32_t* masks,
+                uint64_t* counts);
+int audit_frontier(rtla_ctx* x, int succ, bool pred, const AuditLaunch& launch, rtla_audit_stats* out);
 // rtla_rows.cpp
 int text_threads(int want);
 uint64_t rows_digest(const Layout& L, const uint32_t* rows, size_t n, int threads, bool orbit = false);

@@ -149,6 +149,7 @@ extern "C" void rtla_close(rtla_ctx* x) {
   if (x->sim.ev0) (void)hipEventDestroy(x->sim.ev0);
   if (x->sim.ev1) (void)hipEventDestroy(x->sim.ev1);
   if (x->audit.ctr) (void)hipFree(x->audit.ctr);
+  if (x->audit.prog) (void)hipFree(x->audit.prog);
   if (x->audit.ev0) (void)hipEventDestroy(x->audit.ev0);
   if (x->audit.ev1) (void)hipEventDestroy(x->audit.ev1);
   comm_close(x);

@@ -14,48 +14,7 @@
 // Both count per invariant bit with ballots into wave-uniform registers, add
 // them to the block's LDS tally once per wave and to the device counters once
 // per block, and report the least violation key with one atomicMin per wave.
-#include "rtla_kdev.h"
-#include "rtla_audit.h"
-
-namespace {
-
-constexpr int AUDIT_HEAD = 8;  // the block's tally: u32 words at the start of the dynamic LDS (32 bytes)
-
-// Rows of a k_audit_state staging tile: the most (a power of two <= 64) that fit in 12 KB per wave
-// (four waves: 48 KB of the 64 KB a block may ask for; configs[1]'s 43-word rows take 10.75 KB).
-__host__ __device__ constexpr int audit_tile_rows(int W) {
-  int tr = 64;
-  while (tr > 4 && tr * W * 4 > 12288) tr >>= 1;
-  return tr;
-}
-
-// Per-bit ballots of `bad` added to the wave-uniform counts; returns the OR over the wave.
-__device__ __forceinline__ int audit_count(int bad, unsigned int (&cnt)[INV_COUNT]) {
-  int any = 0;
-#pragma unroll
-  for (int k = 0; k < INV_COUNT; k++) {
-    const int c = __popcll(__ballot(bad >> k & 1));
-    cnt[k] += (unsigned int)c;
-    any |= c ? 1 << k : 0;
-  }
-  return any;
-}
-
-// End of kernel: the wave's counts -> the block's LDS tally -> the device counters; the wave's least key.
-__device__ __forceinline__ void audit_finish(unsigned int* tally, const unsigned int (&cnt)[INV_COUNT],
-                                             unsigned long long evaluated, unsigned long long vkey, AuditCounters* ctr,
-                                             int lane) {
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < INV_COUNT; k++)
-      if (cnt[k]) atomicAdd(&tally[k], cnt[k]);
-    if (evaluated) atomicAdd(&ctr->evaluated, evaluated);
-    if (vkey != AUDIT_NO_VIOLATION) atomicMin(&ctr->viol_key, vkey);
-  }
-  cover_flush(tally, INV_COUNT, ctr->counts);
-}
-
-}  // namespace
+#include "rtla_kaudit.h"
 
 // Rows [0, n) of `cur`; masks (may be null): the violated mask of each row.
 // (A wave's counts are u32: a wave sees far fewer than 2^32 rows.)

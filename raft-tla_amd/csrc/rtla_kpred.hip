@@ -1,0 +1,102 @@
+// rtla_kpred.hip -- user-defined predicates on the GPU: one compiled predicate
+// set (rtla_pred.h's bytecode) evaluated on a batch of rows or on the frontier
+// in HBM.  k_audit_state's memory shape (rtla_kaudit.hip): a wave takes 64
+// consecutive rows, stages them (in tiles of `tr` rows) into LDS with 16-byte
+// loads, each lane interprets the program on its own row there, per-bit ballots
+// go into wave-uniform counts, the block's LDS tally and the device counters
+// once per block, and the least violation key is one atomicMin per wave.
+//
+// What is the interpreter's own:
+//   * the program is copied once per block into LDS; every lane has its own
+//     program counter (trip counts and short-circuits depend on the row);
+//   * the operand file (PRED_FILE words per lane, indexed at run time) lives in
+//     LDS at the odd per-lane stride PRED_STRIDE: word k of the 64 lanes falls
+//     on different banks, and nothing goes to scratch;
+//   * an evaluation error raises FLAG_SPEC_ERROR in ctr->flags: the call fails
+//     whatever the other lanes found.
+// LDS of a block of four waves: 32 B tally + 2 KB program + 4 tiles of at most
+// PRED_TILE_BYTES + 4 * 64 operand files of 92 B = 64,544 B of the 64 KB.
+#include "rtla_kaudit.h"
+#include "rtla_pred.h"
+
+namespace {
+
+constexpr int PRED_STRIDE = PRED_FILE + 1;  // words between two lanes' operand files: odd
+constexpr int PRED_WPB = 4;
+constexpr int PRED_TILE_BYTES = 9728;       // staging tile per wave
+static_assert(PRED_STRIDE % 2 == 1, "conflict-free operand files need an odd stride");
+static_assert((AUDIT_HEAD + PRED_MAX_WORDS + PRED_WPB * 64 * PRED_STRIDE) * 4 + PRED_WPB * PRED_TILE_BYTES <= 65536,
+              "a block's LDS");
+static_assert(4 * WMAX * 4 <= PRED_TILE_BYTES, "the widest row's smallest tile fits");
+static_assert((AUDIT_HEAD + PRED_MAX_WORDS) % 4 == 0, "tiles start 16-byte aligned");
+
+}  // namespace
+
+// Rows [0, n) of `cur`; masks (may be null): the false-definition mask of each row.
+template <int NS>
+__global__ void __launch_bounds__(64 * PRED_WPB)
+k_pred_state(Layout L, Ring cur, unsigned long long n, int tr, const uint32_t* __restrict__ prog, int nwords,
+             int* __restrict__ masks, AuditCounters* ctr) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int W = L.W;
+  uint32_t* const code = lds + AUDIT_HEAD;
+  uint32_t* const tile = code + PRED_MAX_WORDS + wave * tr * W;
+  int* const file = reinterpret_cast<int*>(code + PRED_MAX_WORDS + wpb * tr * W) + (wave * 64 + lane) * PRED_STRIDE;
+  for (int k = threadIdx.x; k < nwords; k += blockDim.x) code[k] = prog[k];
+  cover_zero(lds, AUDIT_HEAD);  // (its barrier also publishes the program)
+
+  unsigned int cnt[PRED_MAX_DEFS] = {};
+  unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
+  const unsigned long long ngroup = (n + 63) >> 6;
+  for (unsigned long long g = (unsigned long long)blockIdx.x * wpb + wave; g < ngroup;
+       g += (unsigned long long)gridDim.x * wpb) {
+    const int nv = (int)min<unsigned long long>(64ull, n - (g << 6));
+    for (int r0 = 0; r0 < nv; r0 += tr) {
+      const int nt = min(tr, nv - r0);
+      const unsigned long long first = (g << 6) + r0;
+      copy_words_lds16(tile, ring_row(cur, first, W), nt * W, lane);
+      wave_sync();
+      int bad = 0;
+      if (lane < nt) {
+        int err = 0;
+        bad = pred_eval<NS>(L, (const uint32_t*)(tile + lane * W), (const uint32_t*)code, file, &err);
+        if (err) {
+          atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
+          bad = 0;
+        }
+        if (masks) masks[first + lane] = bad;
+      }
+      const unsigned long long mb = __ballot(bad != 0);
+      if (mb) {
+        audit_count(bad, cnt);
+        if (vkey == AUDIT_NO_VIOLATION) {  // groups and tiles ascend: the wave's first is its least
+          const int fl = __builtin_ctzll(mb);
+          vkey = pred_key(first + fl, __shfl(bad, fl));
+        }
+      }
+      evaluated += nt;
+      wave_sync();
+    }
+  }
+  audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
+}
+
+namespace rtla {
+
+hipError_t launch_pred(const Layout& L, const Ring& cur, uint64_t n, const uint32_t* prog, int nwords, int* masks,
+                       AuditCounters* ctr, hipStream_t st) {
+  if (!n) return hipSuccess;
+  if (nwords < 1 || nwords > PRED_MAX_WORDS) return hipErrorInvalidValue;
+  const int tr = audit_tile_rows(L.W, PRED_TILE_BYTES);
+  const uint64_t ngroup = (n + 63) / 64;
+  const unsigned grid = (unsigned)std::min<uint64_t>((ngroup + PRED_WPB - 1) / PRED_WPB, (uint64_t)device_cus() * 4);
+  const size_t lds = (size_t)(AUDIT_HEAD + PRED_MAX_WORDS + PRED_WPB * tr * L.W + PRED_WPB * 64 * PRED_STRIDE) *
+                     sizeof(uint32_t);
+  RTLA_DISPATCH_N(L, k_pred_state, dim3(grid), dim3(64 * PRED_WPB), lds, st, L, cur, (unsigned long long)n, tr, prog,
+                  nwords, masks, ctr);
+  return hipGetLastError();
+}
+
+}  // namespace rtla

@@ -1,0 +1,23 @@
+// rtla_predc.h -- a compiled predicate set and the compiler's entry point
+// (rtla_pred.cpp: host only, no HIP).  The C ABI around them (rtla_pred_*) is
+// rtla_predhost.cpp.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "rtla_pred.h"
+
+struct rtla_pred {
+  rtla::Layout L{};                // the layout the set was compiled for (and is bound to)
+  std::vector<uint32_t> code;      // the program, P_HALT last
+  std::vector<std::string> names;  // definition k = bit k
+  uint64_t steps = 0;              // worst-case instructions per row
+  int depth = 0;                   // operand depth reached
+};
+
+namespace rtla {
+
+// Compiles `text` (len bytes) for layout L.  false: *err = "line:col: message".
+bool pred_compile(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err);
+
+}  // namespace rtla

@@ -1,0 +1,122 @@
+// rtla_predhost.cpp -- user-defined predicates: the rtla_pred_* ABI.  The
+// compiler is rtla_pred.cpp (host only), the interpreter rtla_pred.h -- run
+// here per row by rtla_pred_replay, and by the kernel of rtla_kpred.hip for
+// rtla_pred_batch and rtla_pred_frontier, which are the audit's batch and
+// frontier passes (rtla_audit.cpp) with that kernel.
+#include <atomic>
+#include <thread>
+
+#include "rtla_ctx.h"
+#include "rtla_predc.h"
+
+extern "C" int rtla_pred_compile(const rtla_cfg* c, const char* text, rtla_pred** out, char* err, size_t errcap) {
+  if (err && errcap) err[0] = 0;
+  if (!text || !out) return RTLA_E_ARG;
+  *out = nullptr;
+  CFG_LAYOUT(L, c);
+  rtla_pred* p = new rtla_pred;
+  std::string msg;
+  if (!pred_compile(L, text, strlen(text), p, &msg)) {
+    delete p;
+    if (err && errcap) snprintf(err, errcap, "%s", msg.c_str());
+    return RTLA_E_ARG;
+  }
+  *out = p;
+  return RTLA_OK;
+}
+
+extern "C" void rtla_pred_free(rtla_pred* p) { delete p; }
+
+extern "C" int rtla_pred_count(const rtla_pred* p) { return p ? (int)p->names.size() : RTLA_E_ARG; }
+
+extern "C" int rtla_pred_name(const rtla_pred* p, int k, char* buf, size_t cap) {
+  if (!p || !buf || k < 0 || k >= (int)p->names.size() || p->names[(size_t)k].size() + 1 > cap) return RTLA_E_ARG;
+  memcpy(buf, p->names[(size_t)k].c_str(), p->names[(size_t)k].size() + 1);
+  return (int)p->names[(size_t)k].size();
+}
+
+// A set is bound to the row format it was compiled for: the model's bounds and capacities (make_layout derives
+// every offset and width from them).
+static bool pred_bound_to(const rtla_pred* p, const Layout& L) {
+  const Layout& q = p->L;
+  return q.N == L.N && q.V == L.V && q.T == L.T && q.L == L.L && q.C == L.C && q.M == L.M && q.K == L.K &&
+         q.E == L.E && q.W == L.W;
+}
+// The layout of *c, if `p` was compiled for it.
+static int pred_layout(const rtla_cfg* c, const rtla_pred* p, Layout* L) {
+  if (int r = layout_from_cfg(c, L)) return r;
+  return p && pred_bound_to(p, *L) ? RTLA_OK : RTLA_E_ARG;
+}
+
+extern "C" int rtla_pred_replay(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int threads,
+                                int32_t* masks, uint64_t* counts) {
+  Layout L;
+  if (int r = pred_layout(c, p, &L)) return r;
+  if (threads < 0 || !masks || (n && !rows)) return RTLA_E_ARG;
+  const int nt = (int)std::min<size_t>((size_t)std::min(text_threads(threads), 16), std::max<size_t>(1, n / 256));
+  std::vector<AuditCounters> part((size_t)nt, audit_zero());
+  std::atomic<size_t> next{0};
+  auto work = [&](int t) {
+    AuditCounters& tl = part[(size_t)t];
+    int file[PRED_FILE];
+    for (;;) {
+      const size_t b = next.fetch_add(256);
+      if (b >= n) break;
+      for (size_t k = b; k < std::min(n, b + 256); k++) {
+        int err = 0;
+        const int bad = pred_eval<0>(L, rows + k * (size_t)L.W, p->code.data(), file, &err);
+        if (err) tl.flags |= FLAG_SPEC_ERROR;
+        masks[k] = err ? 0 : bad;
+        if (!err)
+          for (int d = 0; d < PRED_MAX_DEFS; d++) tl.counts[d] += bad >> d & 1;
+      }
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
+  work(0);
+  for (auto& th : pool) th.join();
+  int flags = 0;
+  uint64_t sum[AUDIT_COUNTS] = {};
+  for (const AuditCounters& q : part) {
+    flags |= q.flags;
+    for (int k = 0; k < AUDIT_COUNTS; k++) sum[k] += q.counts[k];
+  }
+  if (flags) return flags_to_status(flags);
+  if (counts)
+    for (int k = 0; k < AUDIT_COUNTS; k++) counts[k] = sum[k];
+  return RTLA_OK;
+}
+
+extern "C" int rtla_pred_batch(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int32_t* masks,
+                               uint64_t* counts) {
+  Layout L;
+  if (int r = pred_layout(c, p, &L)) return r;
+  if (!masks || (n && !rows)) return RTLA_E_ARG;
+  uint32_t* d_prog = nullptr;
+  const size_t bytes = p->code.size() * sizeof(uint32_t);
+  HIPCHK(hipMalloc(&d_prog, bytes));
+  int rc = RTLA_E_HIP;
+  if (hipMemcpy(d_prog, p->code.data(), bytes, hipMemcpyHostToDevice) == hipSuccess)
+    rc = audit_batch(L, rows, n, [&](const Ring& cur, uint64_t nr, int* m, AuditCounters* ctr, hipStream_t st) {
+      return launch_pred(L, cur, nr, d_prog, (int)p->code.size(), m, ctr, st);
+    }, masks, counts);
+  (void)hipFree(d_prog);
+  return rc;
+}
+
+extern "C" int rtla_pred_frontier(rtla_ctx* x, const rtla_pred* p, rtla_audit_stats* out) {
+  if (!x || !p) return RTLA_E_ARG;
+  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
+      x->sh[0].n_cur == 0)
+    return RTLA_E_STATE;
+  const Layout L = x->L;
+  if (!pred_bound_to(p, L)) return RTLA_E_ARG;
+  HIPCHK(hipSetDevice(x->device));
+  AuditState& a = x->audit;
+  if (!a.prog) HIPCHK(hipMalloc((void**)&a.prog, PRED_MAX_WORDS * sizeof(uint32_t)));
+  HIPCHK(hipMemcpyAsync(a.prog, p->code.data(), p->code.size() * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
+  return audit_frontier(x, 0, true, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
+    return launch_pred(L, cur, n, a.prog, (int)p->code.size(), m, ctr, st);
+  }, out);
+}

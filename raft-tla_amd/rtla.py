@@ -35,6 +35,7 @@ COVER_NAMES = ["Restart", "Timeout", "RequestVote", "BecomeLeader", "ClientReque
 
 # rtla_level_stats.flags: which capacity ran out (include/rtla.h RTLA_CAP_*)
 CAP_NAMES = {1: "spec-error", 2: "row", 4: "frontier", 8: "fpset", 16: "outbox"}
+CAP_SPEC_ERROR = 1
 
 
 class RtlaError(RuntimeError):
@@ -142,6 +143,14 @@ def _load():
         "rtla_check_frontier": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(_AuditStats)]),
         "rtla_fpset_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                        P(C.c_int32)]),
+        "rtla_pred_compile": (C.c_int, [P(_Cfg), C.c_char_p, P(C.c_void_p), C.c_char_p, C.c_size_t]),
+        "rtla_pred_free": (None, [C.c_void_p]),
+        "rtla_pred_count": (C.c_int, [C.c_void_p]),
+        "rtla_pred_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
+        "rtla_pred_replay": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, C.c_int, P(C.c_int32),
+                                       P(C.c_uint64)]),
+        "rtla_pred_batch": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, P(C.c_int32), P(C.c_uint64)]),
+        "rtla_pred_frontier": (C.c_int, [C.c_void_p, C.c_void_p, P(_AuditStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -161,7 +170,8 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_rows_text_hash", "rtla_level_text_hash", "rtla_row_layout", "rtla_rows_orbit_hash",
             "rtla_level_orbit_hash", "rtla_orbit_text", "rtla_probe_bench3", "rtla_random_texts",
             "rtla_frontier_rows", "rtla_simulate", "rtla_sim_replay", "rtla_sim_walk", "rtla_check_batch",
-            "rtla_check_replay", "rtla_check_frontier", "rtla_fpset_probe"]
+            "rtla_check_replay", "rtla_check_frontier", "rtla_fpset_probe", "rtla_pred_compile", "rtla_pred_free",
+            "rtla_pred_count", "rtla_pred_name", "rtla_pred_replay", "rtla_pred_batch", "rtla_pred_frontier"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -369,6 +379,76 @@ def _check(st: int, what: str):
     return st
 
 
+class Predicates:
+    """A compiled set of user-defined state predicates (rtla_pred_compile):
+    `text` holds up to 8 definitions `Name == expr` in the predicate language
+    (specs/MCPredicates.tla), compiled for cfg's row
+    layout.  A syntax, type or bound error raises RtlaError(E_ARG) whose
+    message starts with line:col.  Use as a context manager, or leave it to
+    the garbage collector."""
+
+    def __init__(self, cfg: Config, text: str):
+        self.cfg = cfg
+        self._h = None
+        cc = cfg.c()
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = _lib.rtla_pred_compile(C.byref(cc), text.encode(), C.byref(h), err, len(err))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_pred_compile: " + err.value.decode() if err.value else "rtla_pred_compile")
+        self._h = h
+        buf = C.create_string_buffer(256)
+        self.names: List[str] = []
+        for k in range(_check(_lib.rtla_pred_count(h), "rtla_pred_count")):
+            _check(_lib.rtla_pred_name(h, k, buf, len(buf)), "rtla_pred_name")
+            self.names.append(buf.value.decode())
+
+    def names_of(self, mask: int) -> List[str]:
+        """The names of a mask's definitions, in definition order."""
+        return [n for k, n in enumerate(self.names) if mask >> k & 1]
+
+    def close(self):
+        if self._h:
+            _lib.rtla_pred_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pred_rows(fn, what: str, preds: Predicates, rows, *extra):
+    cc = preds.cfg.c()
+    flat, n = _flat_rows(rows, row_words(preds.cfg))
+    masks = (C.c_int32 * max(1, n))()
+    counts = (C.c_uint64 * 8)()
+    rc = fn(C.byref(cc), preds._h, flat, n, *extra, masks, counts)
+    if rc < 0:
+        raise RtlaError(rc, what, CAP_SPEC_ERROR if rc == E_SPEC else 0)
+    return list(masks[:n]), {nm: counts[k] for k, nm in enumerate(preds.names)}
+
+
+def pred_replay(preds: Predicates, rows, threads: int = 0):
+    """A predicate set evaluated on the host (rtla_pred_replay; no GPU, no
+    context): (masks, counts) -- masks[k] the definitions FALSE on rows[k] (bit
+    d = preds.names[d]), counts[name] the rows on which it is false.  An
+    evaluation error raises RtlaError(E_SPEC)."""
+    return _pred_rows(_lib.rtla_pred_replay, "rtla_pred_replay", preds, rows, threads)
+
+
+def pred_batch(preds: Predicates, rows):
+    """The same on the GPU (rtla_pred_batch: rtla_kpred.hip)."""
+    return _pred_rows(_lib.rtla_pred_batch, "rtla_pred_batch", preds, rows)
+
+
 def row_words(cfg: Config) -> int:
     cc = cfg.c()
     return _check(_lib.rtla_row_words(C.byref(cc)), "rtla_row_words")
@@ -560,6 +640,7 @@ class Checker:
         _check(_lib.rtla_open(C.byref(self._cc), rank, world, cid, C.byref(h)), "rtla_open")
         self._h = h
         self._recovered = False
+        self._pred_viol: Optional[List[str]] = None  # the false definitions of the last audit_predicates violation
         self.levels: List[Level] = []
         self.status = OK
 
@@ -598,6 +679,7 @@ class Checker:
 
     def reset(self):
         _check(_lib.rtla_reset(self._h), "rtla_reset")
+        self._pred_viol = None
         self.levels = []
         self.status = OK
 
@@ -605,6 +687,7 @@ class Checker:
         """One BFS level.  Raises RtlaError (with .flags naming the capacity
         that ran out) if the level could not be completed."""
         st = _Stats()
+        self._pred_viol = None
         rc = _lib.rtla_step(self._h, C.byref(st))
         if rc < 0:
             self.status = rc
@@ -613,17 +696,30 @@ class Checker:
         self._rec(st)
         return self.status
 
-    def run(self, max_levels: int = 100000) -> int:
+    def run(self, max_levels: int = 100000, predicates: Optional[Predicates] = None) -> int:
+        """BFS until the search ends, a violation or max_levels.  predicates: a
+        set audited on every level right after it is produced, Init's included
+        (audit_predicates); the run stops with VIOLATION at the first level that
+        holds a state on which a definition is false."""
+        def audited() -> int:
+            if predicates is not None and self.status == OK and self.levels[-1].new > 0:
+                if self.audit_predicates(predicates).status == VIOLATION:
+                    self.status = VIOLATION
+            return self.status
+
         if not self.levels and not self._recovered:
-            if self.init() != OK:
+            if self.init() != OK or audited() != OK:
                 return self.status
         while self.status == OK and len(self.levels) < max_levels:
             self.step()
+            audited()
         return self.status
 
     def violation(self):
         m, im = C.c_int32(0), C.c_int32(0)
         _lib.rtla_violation(self._h, C.byref(m), C.byref(im))
+        if self._pred_viol is not None:  # (definition bits, not RTLA_INV_*)
+            return ", ".join(self._pred_viol), bool(im.value)
         names = [n for n, b in INV_BITS.items() if m.value & b]
         return (names[0] if names else None), bool(im.value)
 
@@ -736,6 +832,7 @@ class Checker:
         a VIOLATION result, violation() and trace() give the counterexample."""
         buf = (C.c_uint64 * max(1, 4 * n_walks))() if ends else None
         st = _SimStats()
+        self._pred_viol = None
         rc = _lib.rtla_simulate(self._h, seed, first, n_walks, depth, buf, C.byref(st))
         if rc < 0:
             raise RtlaError(rc, "rtla_simulate", st.flags)
@@ -748,6 +845,7 @@ class Checker:
         untouched; after a VIOLATION result, violation() and trace() give the
         counterexample (for succ, ending in the violating successor)."""
         st = _AuditStats()
+        self._pred_viol = None
         rc = _lib.rtla_check_frontier(self._h, inv_mask_of(invariants), int(succ), C.byref(st))
         if rc < 0:
             raise RtlaError(rc, "rtla_check_frontier", st.flags)
@@ -760,6 +858,26 @@ class Checker:
             res.viol_mask, res.viol_in_model = st.viol_mask, bool(st.viol_in_model)
         return res
 
+    def audit_predicates(self, preds: Predicates) -> AuditResult:
+        """Evaluate a compiled predicate set over the states of the level last
+        produced, in place on the GPU (rtla_pred_frontier).  counts and
+        violation name definitions; otherwise as audit(): the BFS is left
+        untouched, and after a VIOLATION result violation() and trace() give the
+        counterexample, until the next step, audit or simulation."""
+        st = _AuditStats()
+        self._pred_viol = None
+        rc = _lib.rtla_pred_frontier(self._h, preds._h, C.byref(st))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_pred_frontier", st.flags)
+        res = AuditResult(status=rc, audited=st.audited, evaluated=st.evaluated, kernel_ms=st.kernel_ms,
+                          row_bytes=st.row_bytes, counts={nm: st.counts[k] for k, nm in enumerate(preds.names)})
+        if rc == VIOLATION:
+            res.violation = preds.names_of(st.viol_mask)
+            res.viol_index, res.viol_inst = st.viol_index, st.viol_inst
+            res.viol_mask, res.viol_in_model = st.viol_mask, bool(st.viol_in_model)
+            self._pred_viol = res.violation
+        return res
+
     def coverage(self) -> dict:
         n = len(COVER_NAMES)
         g, d = (C.c_uint64 * n)(), (C.c_uint64 * n)()
@@ -767,10 +885,12 @@ class Checker:
         return {COVER_NAMES[k]: (g[k], d[k]) for k in range(n)}
 
 
-def check(cfg: Config, trace: bool = True) -> Result:
-    """Exhaustive BFS of the model (TLC `-workers N` breadth-first mode)."""
+def check(cfg: Config, trace: bool = True, predicates: Optional[Predicates] = None) -> Result:
+    """Exhaustive BFS of the model (TLC `-workers N` breadth-first mode).
+    predicates: user-defined invariants checked on every level (Checker.run);
+    Result.violation then names the false definitions."""
     with Checker(cfg) as ck:
-        st = ck.run()
+        st = ck.run(predicates=predicates)
         res = Result(distinct=ck.distinct, generated=ck.generated, levels=list(ck.levels))
         res.depth = sum(1 for lv in ck.levels if lv.new > 0)
         res.seconds = sum(lv.seconds for lv in ck.levels)
