@@ -47,6 +47,10 @@
  *                            INVARIANT: a predicate in a TLA+ subset over the
  *                            spec's variables, compiled to a bounded bytecode
  *                            and evaluated by one interpreter on host and GPU.
+ *   rtla_pred_compile_step,
+ *   rtla_pred_step_frontier ... an action property `Name == [][A]_vars` named
+ *                            under PROPERTY: the same bytecode over a step's two
+ *                            states, checked on every step out of a BFS level.
  *   rtla_sim_replay,
  *   rtla_sim_walk            the same walks recomputed on the host from
  *                            (seed, walk id): reproduce one behaviour, as TLC
@@ -361,6 +365,41 @@ int rtla_pred_replay(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *ro
 int rtla_pred_batch(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *rows, size_t n, int32_t *masks,
                     uint64_t *counts);
 int rtla_pred_frontier(rtla_ctx *ctx, const rtla_pred *p, rtla_audit_stats *out);
+
+/* Action properties (TLC: `Name == [][expr]_vars` named under PROPERTY).  An
+ * action definition is a predicate over a step: inside the brackets the spec's
+ * variables may carry a prime and then read the successor (grammar, typing of
+ * the two rows and the semantics: DESIGN.md section 14; examples:
+ * specs/MCActions.tla).  rtla_pred_compile_step compiles the action definitions
+ * of `text` (at most 8) into a set of the step kind; the state definitions of
+ * the same text are parsed and type-checked but skipped.  Errors as
+ * rtla_pred_compile's, and RTLA_E_ARG if the text holds no action definition.
+ * rtla_pred_is_step: 1 for such a set, 0 for rtla_pred_compile's.  A set knows
+ * its kind: a state set given to a step call is RTLA_E_ARG, and so is a step
+ * set given to rtla_pred_replay / _batch / _frontier.
+ * What is evaluated: for each row s, every action instance in ascending
+ * instance number (as rtla_check_replay with succ = 1); each enabled successor
+ * t, in-model or not, is one evaluated step.  Definition k is false on the step
+ * iff its expression is FALSE on (s, t) and t is not s (their 128-bit
+ * fingerprints differ: a stuttering step satisfies every [A]_vars).  masks[k]
+ * is the OR over the steps out of row k, counts[d] the steps on which
+ * definition d is false, *evaluated (may be NULL) the steps.  A successor's
+ * spec or row-capacity error and a program's evaluation error on any step
+ * (a stuttering one included) fail the call, on host and device alike.
+ * rtla_pred_step_replay: on the host; rtla_pred_step_batch: on the GPU,
+ * stateless; rtla_pred_step_frontier: over the steps out of the current
+ * frontier, in place, with rtla_check_frontier's preconditions, touching
+ * nothing of the search; out->audited is the rows, out->evaluated the steps,
+ * viol_index / viol_inst / viol_in_model the least (row, instance) with a false
+ * definition as for succ = 1, viol_mask its definition bits.  After
+ * RTLA_VIOLATION rtla_trace gives the BFS parent chain from Init to s, then t. */
+int rtla_pred_compile_step(const rtla_cfg *cfg, const char *text, rtla_pred **out, char *err, size_t errcap);
+int rtla_pred_is_step(const rtla_pred *p);
+int rtla_pred_step_replay(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *rows, size_t n, int threads,
+                          int32_t *masks, uint64_t *counts, uint64_t *evaluated);
+int rtla_pred_step_batch(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *rows, size_t n, int32_t *masks,
+                         uint64_t *counts, uint64_t *evaluated);
+int rtla_pred_step_frontier(rtla_ctx *ctx, const rtla_pred *p, rtla_audit_stats *out);
 
 /* Diagnostic (performance analysis only): re-expand the current frontier
  * `reps` times with the level kernel's experiment switches `xflags` (XF_*

@@ -61,7 +61,7 @@ extern "C" int rtla_check_replay(const rtla_cfg* c, const uint32_t* rows, size_t
 // Stateless, like rtla_expand_batch: the rows are staged into a device buffer
 // of their own (test-sized inputs).
 int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaunch& launch, int32_t* masks,
-                uint64_t* counts) {
+                uint64_t* counts, uint64_t* evaluated) {
   const uint64_t cap = round64(std::max<size_t>(n, 1));
   uint32_t* d_rows = nullptr;
   int* d_masks = nullptr;
@@ -87,6 +87,7 @@ int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaun
     return flags_to_status(h.flags);
   }
   audit_counts_out(h, counts);
+  if (evaluated) *evaluated = h.evaluated;
   return RTLA_OK;
 }
 
@@ -100,7 +101,8 @@ extern "C" int rtla_check_batch(const rtla_cfg* c, const uint32_t* rows, size_t 
   }, masks, counts);
 }
 
-int audit_frontier(rtla_ctx* x, int succ, bool pred, const AuditLaunch& launch, rtla_audit_stats* out) {
+int audit_frontier(rtla_ctx* x, int succ, int kind, const AuditLaunch& launch, rtla_audit_stats* out) {
+  const bool step = kind == AUDIT_PRED_STEP;
   if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
       x->sh[0].n_cur == 0)
     return RTLA_E_STATE;
@@ -128,10 +130,10 @@ int audit_frontier(rtla_ctx* x, int succ, bool pred, const AuditLaunch& launch, 
   } else if (h.viol_key != AUDIT_NO_VIOLATION) {
     status = RTLA_VIOLATION;
     a.viol = true;
-    a.start = s.cur_base + audit_key_index(h.viol_key);
-    a.inst = succ ? audit_key_inst(h.viol_key) : -1;
-    a.mask = pred ? pred_key_mask(h.viol_key) : audit_key_mask(h.viol_key);
-    a.in_model = pred ? 1 : audit_key_in_model(h.viol_key);
+    a.start = s.cur_base + (step ? step_key_index(h.viol_key) : audit_key_index(h.viol_key));
+    a.inst = !succ ? -1 : step ? step_key_inst(h.viol_key) : audit_key_inst(h.viol_key);
+    a.mask = kind != AUDIT_INVARIANTS ? pred_key_mask(h.viol_key) : audit_key_mask(h.viol_key);
+    a.in_model = step ? step_key_in_model(h.viol_key) : kind == AUDIT_PRED_STATE ? 1 : audit_key_in_model(h.viol_key);
   }
   if (out) {
     memset(out, 0, sizeof *out);
@@ -144,7 +146,7 @@ int audit_frontier(rtla_ctx* x, int succ, bool pred, const AuditLaunch& launch, 
     out->viol_index = ~0ull;
     out->viol_inst = -1;
     if (a.viol) {
-      out->viol_index = audit_key_index(h.viol_key);
+      out->viol_index = a.start - s.cur_base;
       out->viol_inst = a.inst;
       out->viol_mask = a.mask;
       out->viol_in_model = a.in_model;
@@ -163,7 +165,7 @@ extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, 
   if (!audit_args_ok(inv_mask, succ)) return RTLA_E_ARG;
   Layout L = x->L;
   L.inv_mask = inv_mask;
-  return audit_frontier(x, succ, false, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
+  return audit_frontier(x, succ, AUDIT_INVARIANTS, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
     return launch_audit(L, cur, n, succ, m, ctr, st);
   }, out);
 }

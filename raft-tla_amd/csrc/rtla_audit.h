@@ -35,6 +35,15 @@ RTLA_HD int audit_key_mask(uint64_t key) { return (int)(key & INV_ALL); }
 // eight bits are the row's false definitions (rtla_audit_stats.counts has eight).
 RTLA_HD uint64_t pred_key(uint64_t index, int mask) { return index << 24 | (uint64_t)(mask & 255); }
 RTLA_HD int pred_key_mask(uint64_t key) { return (int)(key & 255); }
+// The key of a step audit (k_pred_step): row index << 25 | instance << 9 | in_model << 8 |
+// the step's false action definitions.  The low nine bits are a function of (row, instance).
+RTLA_HD uint64_t step_key(uint64_t index, int inst, int in_model, int mask) {
+  return index << 25 | (uint64_t)inst << 9 | (uint64_t)(in_model ? 256 : 0) | (uint64_t)(mask & 255);
+}
+RTLA_HD uint64_t step_key_index(uint64_t key) { return key >> 25; }
+RTLA_HD int step_key_inst(uint64_t key) { return (int)(key >> 9 & 0xffff); }
+RTLA_HD int step_key_in_model(uint64_t key) { return (int)(key >> 8 & 1); }
+enum AuditKind { AUDIT_INVARIANTS = 0, AUDIT_PRED_STATE, AUDIT_PRED_STEP };  // which key an audit launch reports
 
 // Device counters of one audit launch (the host's tally has the same shape).
 struct AuditCounters {

@@ -21,6 +21,9 @@
 // a name under INVARIANT(S) or -audit that is not built in is looked up in FILE
 // (the predicate language of DESIGN.md section 13), compiled, and checked on
 // every level of the search right after it is produced (-gpus 1 only).
+// A name under PROPERTY / PROPERTIES is accepted when it is an action definition
+// `Name == [][A]_vars` of FILE: it is checked on every
+// step out of every level; -audit may name one too (the steps out of the last level).
 //
 // SPEC.tla is either the reference's raft.tla (sha256 checked: the semantics
 // are compiled into the kernels, not parsed) or a wrapper module that
@@ -124,6 +127,8 @@ struct CfgFile {
   std::string specification;
   std::string symmetry;  // SYMMETRY operator name ("" = none)
   std::vector<std::string> invariants, constraints;
+  std::vector<std::string> properties;  // PROPERTY / PROPERTIES names (action definitions of the -predicates file)
+  std::string property_keyword;         // the keyword they stood under, for the refusal
   std::map<std::string, std::vector<std::string>> sets;  // Name = {a, b}
   std::map<std::string, std::string> scalars;            // Name = "x" | 3 | mv
 };
@@ -199,8 +204,13 @@ bool parse_cfg(const std::string& text, CfgFile* c, std::string* err) {
       continue;
     }
     if (mode == "SYMMETRY") { c->symmetry = t[i++]; continue; }
-    if (mode == "VIEW" || mode == "PROPERTY" || mode == "PROPERTIES" || mode == "INIT" ||
-        mode == "NEXT" || mode == "ACTION_CONSTRAINT" || mode == "ACTION_CONSTRAINTS") {
+    if (mode == "PROPERTY" || mode == "PROPERTIES") {  // (accepted or refused once the predicate file is known)
+      c->property_keyword = mode;
+      c->properties.push_back(t[i++]);
+      continue;
+    }
+    if (mode == "VIEW" || mode == "INIT" || mode == "NEXT" || mode == "ACTION_CONSTRAINT" ||
+        mode == "ACTION_CONSTRAINTS") {
       *err = mode + " is not supported by this checker";
       return false;
     }
@@ -223,7 +233,10 @@ void usage() {
           "  D steps (default 100) from the states of level K; walk ids F .. F+N-1 are global, so runs with\n"
           "  disjoint ranges and the same seed compose; one GPU only.\n"
           "  -predicates FILE: definitions in the predicate language (specs/MCPredicates.tla) that INVARIANT(S) and\n"
-          "          -audit may name beside the built-in invariants; checked on every level of the search (-gpus 1)\n"
+          "          -audit may name beside the built-in invariants; checked on every level of the search (-gpus 1).\n"
+          "          Its action definitions `Name == [][A]_vars` (specs/MCActions.tla) may be named under\n"
+          "          PROPERTY / PROPERTIES, and are then checked on every step out of every level, or under -audit\n"
+          "          (the steps out of the last level)\n"
           "  -audit: when the BFS stops (exhausted, out of capacity, or after -bfs-levels K) evaluate the named\n"
           "  invariants -- any of the specification's, not only the cfg's -- over the states of the last level;\n"
           "  one GPU only.\n");
@@ -370,10 +383,15 @@ int32_t invariant_bit(const std::string& name) {
 // `text` with every definition whose name is not in `keep` blanked out (line breaks kept, so a compile error's
 // line:col is the file's): the set compiled is the set named, and only it is evaluated.  A definition starts at
 // an identifier followed by `==` outside comments and ends where the next one, or the module's closing line, starts.
-std::string select_definitions(const std::string& text, const std::vector<std::string>& keep) {
-  struct Def { size_t at; std::string name; };
+struct Def {
+  size_t at;
+  std::string name;
+  bool action;  // Name == [][ ... ]_vars
+};
+// The definitions of a predicate file, in file order; *end: where the module's closing line starts.
+std::vector<Def> scan_definitions(const std::string& text, size_t* end) {
   std::vector<Def> defs;
-  size_t end = text.size();
+  *end = text.size();
   for (size_t i = 0; i < text.size();) {
     if (text.compare(i, 2, "\\*") == 0) {
       while (i < text.size() && text[i] != '\n') i++;
@@ -385,19 +403,29 @@ std::string select_definitions(const std::string& text, const std::vector<std::s
         else i++;
       } while (deep > 0 && i < text.size());
     } else if (text.compare(i, 4, "====") == 0) {
-      end = i;
+      *end = i;
       break;
     } else if (isalpha((unsigned char)text[i]) || text[i] == '_') {
       size_t j = i;
       while (j < text.size() && (isalnum((unsigned char)text[j]) || text[j] == '_')) j++;
       size_t k = j;
       while (k < text.size() && (text[k] == ' ' || text[k] == '\t')) k++;
-      if (text.compare(k, 2, "==") == 0 && text.compare(k, 3, "===") != 0) defs.push_back({i, text.substr(i, j - i)});
+      if (text.compare(k, 2, "==") == 0 && text.compare(k, 3, "===") != 0) {
+        std::string head;  // the body's first three characters that are not blanks
+        for (size_t q = k + 2; q < text.size() && head.size() < 3; q++)
+          if (!isspace((unsigned char)text[q])) head.push_back(text[q]);
+        defs.push_back({i, text.substr(i, j - i), head == "[]["});
+      }
       i = j;
     } else {
       i++;
     }
   }
+  return defs;
+}
+std::string select_definitions(const std::string& text, const std::vector<std::string>& keep) {
+  size_t end = 0;
+  const std::vector<Def> defs = scan_definitions(text, &end);
   std::string out = text;
   for (size_t d = 0; d < defs.size(); d++) {
     if (std::find(keep.begin(), keep.end(), defs[d].name) != keep.end()) continue;
@@ -408,12 +436,39 @@ std::string select_definitions(const std::string& text, const std::vector<std::s
   return out;
 }
 
-// The definitions `names` of the predicate file, compiled for *c; exits as for an undefined invariant.
+// The names of the file's definitions of one kind (action: Name == [][ ... ]_vars), in file order.
+std::vector<std::string> definitions_of_kind(const std::string& text, bool action) {
+  size_t end = 0;
+  std::vector<std::string> out;
+  for (const Def& d : scan_definitions(text, &end))
+    if (d.action == action) out.push_back(d.name);
+  return out;
+}
+
+// The action definitions `names` of the predicate file (PROPERTY, -audit), compiled for *c as a step set.  The
+// caller has checked that every name is an action definition of the file.
+rtla_pred* load_actions(const rtla_cfg* c, const std::string& path, const std::vector<std::string>& names) {
+  bool ok = false;
+  const std::string text = read_file(path, &ok);
+  if (!ok) { printf("Error: cannot read the predicate file %s\n", path.c_str()); exit(150); }
+  char err[512];
+  rtla_pred* set = nullptr;
+  if (rtla_pred_compile_step(c, select_definitions(text, names).c_str(), &set, err, sizeof err) != RTLA_OK) {
+    printf("Error: %s:%s\n", path.c_str(), err[0] ? err : " the configuration is outside the row format");
+    exit(150);
+  }
+  return set;
+}
+
+// The state definitions `names` of the predicate file, compiled for *c; exits as for an undefined invariant.
+// The file is split by kind first: its action definitions are blanked out, INVARIANT names none of them.
 rtla_pred* load_predicates(const rtla_cfg* c, const std::string& path, const std::vector<std::string>& names) {
   std::ifstream in(path);
   if (!in) { printf("Error: cannot read the predicate file %s\n", path.c_str()); exit(150); }
+  std::stringstream file;
+  file << in.rdbuf();
   std::stringstream ss;
-  ss << in.rdbuf();
+  ss << select_definitions(file.str(), definitions_of_kind(file.str(), false));
   char err[512];
   rtla_pred* all = nullptr;
   if (rtla_pred_compile(c, ss.str().c_str(), &all, err, sizeof err) != RTLA_OK) {
@@ -591,6 +646,19 @@ int main(int argc, char** argv) {
   CfgFile cf;
   std::string err;
   if (!parse_cfg(cfg_text, &cf, &err)) { printf("Error: %s: %s\n", cfgpath.c_str(), err.c_str()); return 151; }
+  // PROPERTY names are the action definitions of the -predicates file; anything else is refused as ever
+  std::vector<std::string> action_names;
+  if (!pred_file.empty()) {
+    bool pf_ok = false;
+    action_names = definitions_of_kind(read_file(pred_file, &pf_ok), true);
+  }
+  auto is_action = [&](const std::string& nm) {
+    return std::find(action_names.begin(), action_names.end(), nm) != action_names.end();
+  };
+  if (!cf.properties.empty() && !std::all_of(cf.properties.begin(), cf.properties.end(), is_action)) {
+    printf("Error: %s: %s is not supported by this checker\n", cfgpath.c_str(), cf.property_keyword.c_str());
+    return 151;
+  }
   if (!cf.specification.empty() && cf.specification != "Spec") {
     printf("Error: SPECIFICATION %s: only Spec (raft.tla:469) is supported\n", cf.specification.c_str());
     return 151;
@@ -613,7 +681,9 @@ int main(int argc, char** argv) {
     c.inv_mask |= invariant_bit(inv);
   }
   int32_t audit_mask = 0;
+  std::vector<std::string> audit_actions;  // -audit names that are action definitions of the predicate file
   for (auto& inv : audit_names) {
+    if (is_action(inv)) { audit_actions.push_back(inv); continue; }
     if (!pred_file.empty() && !defined(inv)) { user_audit.push_back(inv); continue; }
     if (!defined(inv) || inv == "StateConstraint") {
       printf("Error: The invariant %s specified in the configuration file is not defined in the specification.\n",
@@ -676,14 +746,22 @@ int main(int argc, char** argv) {
   }
   rtla_pred* preds = user_invs.empty() ? nullptr : load_predicates(&c, pred_file, user_invs);
   rtla_pred* audit_preds = user_audit.empty() ? nullptr : load_predicates(&c, pred_file, user_audit);
+  rtla_pred* actions = cf.properties.empty() ? nullptr : load_actions(&c, pred_file, cf.properties);
+  rtla_pred* audit_acts = audit_actions.empty() ? nullptr : load_actions(&c, pred_file, audit_actions);
   bool pred_violation = false;  // the violation reported is a predicate set's: its mask holds definition bits
   const rtla_pred* viol_set = nullptr;
-  // user-defined invariants: the level just produced is audited in place (rtla_pred_frontier)
+  // user-defined invariants: the level just produced is audited in place (rtla_pred_frontier); then the action
+  // properties on the steps out of it (rtla_pred_step_frontier), so every step out of every reachable in-model
+  // state is checked before the next level is produced
   auto check_level = [&](rtla_ctx* x, int st_level, uint64_t new_states) -> int {
-    if (!preds || st_level != RTLA_OK || new_states == 0) return st_level;
-    const int rc = rtla_pred_frontier(x, preds, nullptr);
-    if (rc == RTLA_VIOLATION) { pred_violation = true; viol_set = preds; }
-    return rc == RTLA_OK ? st_level : rc;
+    if (st_level != RTLA_OK || new_states == 0) return st_level;
+    for (const rtla_pred* set : {(const rtla_pred*)preds, (const rtla_pred*)actions}) {
+      if (!set) continue;
+      const int rc = rtla_pred_is_step(set) ? rtla_pred_step_frontier(x, set, nullptr) : rtla_pred_frontier(x, set, nullptr);
+      if (rc == RTLA_VIOLATION) { pred_violation = true; viol_set = set; }
+      if (rc != RTLA_OK) return rc;
+    }
+    return st_level;
   };
   unsigned char comm_id[128];
   if (world > 1 && !rendezvous(rank, getenv("RTLA_RENDEZVOUS"), false, comm_id)) {
@@ -813,7 +891,32 @@ int main(int argc, char** argv) {
         st = rtla_check_frontier(ctx, audit_mask, 0, &as);
       }
     }
-    secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (audit_acts) {  // action definitions: the steps out of the level
+      rtla_audit_stats ps;
+      memset(&ps, 0, sizeof ps);
+      const int pst = rtla_pred_step_frontier(ctx, audit_acts, &ps);
+      if (pst < 0) {
+        printf("Error: audit: %s\n", rtla_strerror(pst));
+        rtla_close(ctx);
+        return 255;
+      }
+      for (int k = 0; k < rtla_pred_count(audit_acts); k++) {
+        if (ps.counts[k]) printf("Error: Action property %s is violated by %llu of the %llu steps.\n",
+                                 pred_name(audit_acts, k).c_str(), (unsigned long long)ps.counts[k],
+                                 (unsigned long long)ps.evaluated);
+        else printf("Action property %s holds on all %llu steps.\n", pred_name(audit_acts, k).c_str(),
+                    (unsigned long long)ps.evaluated);
+      }
+      if (pst == RTLA_VIOLATION && st != RTLA_VIOLATION) {  // (a violated invariant's trace comes first)
+        st = pst;
+        pred_violation = true;
+        viol_set = audit_acts;
+      } else if (st == RTLA_VIOLATION) {  // (the trace reported is the last audit's: run that one again)
+        if (pred_violation) st = rtla_pred_frontier(ctx, audit_preds, nullptr);
+        else st = rtla_check_frontier(ctx, audit_mask, 0, &as);
+      }
+    }
+    secs =std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   } else if (audit && st == RTLA_DONE) {
     printf("Audit: the search is complete and its last level is empty; nothing to audit.\n");
   }
@@ -856,7 +959,9 @@ int main(int argc, char** argv) {
     rtla_violation(ctx, &mask, &inm);
     if (pred_violation) {
       for (int k = 0; k < rtla_pred_count(viol_set); k++)  // every false definition of the state, in file order
-        if (mask >> k & 1) printf("Error: Invariant %s is violated.\n", pred_name(viol_set, k).c_str());
+        if (mask >> k & 1)
+          printf("Error: %s %s is violated.\n", rtla_pred_is_step(viol_set) ? "Action property" : "Invariant",
+                 pred_name(viol_set, k).c_str());
     } else {
       for (auto& i : INVARIANTS)  // every violated name, in bit order
         if (mask & i.bit) printf("Error: Invariant %s is violated.\n", i.name);

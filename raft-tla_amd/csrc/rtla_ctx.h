@@ -195,13 +195,14 @@ int layout_from_cfg(const rtla_cfg* c, Layout* L);
 bool fault_here(const rtla_ctx* x, const char* where);
 void print_stamps(const DevCounters& c, int level);
 // rtla_audit.cpp: one audit launch (`launch`: the kernel, over the ring, row count, device counters and stream it
-// is given) over host rows staged into a device buffer / over the context's frontier where it lies.  pred: the
-// masks are a predicate set's definition bits (pred_key), not RTLA_INV_*.
+// is given) over host rows staged into a device buffer / over the context's frontier where it lies.  kind
+// (AuditKind): whether the masks are RTLA_INV_* bits (audit_key), a predicate set's definition bits on rows
+// (pred_key) or an action set's on steps (step_key).  evaluated (may be null): the evaluated states / steps.
 using AuditLaunch = std::function<hipError_t(const Ring&, uint64_t, int*, AuditCounters*, hipStream_t)>;
 AuditCounters audit_zero();
 int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaunch& launch, int32_t* masks,
-                uint64_t* counts);
-int audit_frontier(rtla_ctx* x, int succ, bool pred, const AuditLaunch& launch, rtla_audit_stats* out);
+                uint64_t* counts, uint64_t* evaluated = nullptr);
+int audit_frontier(rtla_ctx* x, int succ, int kind, const AuditLaunch& launch, rtla_audit_stats* out);
 // rtla_rows.cpp
 int text_threads(int want);
 uint64_t rows_digest(const Layout& L, const uint32_t* rows, size_t n, int threads, bool orbit = false);

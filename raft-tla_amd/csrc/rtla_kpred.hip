@@ -16,8 +16,11 @@
 //     whatever the other lanes found.
 // LDS of a block of four waves: 32 B tally + 2 KB program + 4 tiles of at most
 // PRED_TILE_BYTES + 4 * 64 operand files of 92 B = 64,544 B of the 64 KB.
+//
+// k_pred_step, below k_pred_state, runs an action set (two rows: a state and a
+// successor materialised in LDS) on every step out of the rows.
 #include "rtla_kaudit.h"
-#include "rtla_pred.h"
+#include "rtla_step.h"
 
 namespace {
 
@@ -83,7 +86,123 @@ k_pred_state(Layout L, Ring cur, unsigned long long n, int tr, const uint32_t* _
   audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
 }
 
+// ---- action properties: an action set on every step out of rows [0, n) of `cur`.
+//
+// k_audit_succ's shape (rtla_kaudit.hip): one wave per state, the parent in LDS (load_parent: with its new
+// allLogs words and the fingerprint they give), each lane the Delta of one candidate instance, the enabled lanes
+// ranked by ballot.  The interpreter reads rows, so the enabled children are materialised (parent + patches, as
+// k_expand_batch's) into a per-wave LDS stage, `tc` at a time, and the lane whose child is in the stage runs
+// pred_eval_rows on (parent row, child row), both in LDS; the child never leaves the CU.  Per wave: parent
+// (even_words(W)) | allLogs' (32) | server hashes (4 * NMAX) | tc children at stride W | 1 (odd: the lanes' reads
+// of word k of their own child fall on different banks) | tc operand files at PRED_STRIDE (indexed by the child's
+// slot: a lane without a child in the stage needs none).
+constexpr int STEP_WPB = 4;
+__host__ __device__ constexpr int step_child_stride(int W) { return W | 1; }
+__host__ __device__ constexpr int step_wave_words(int W, int tc) {
+  return (even_words(W) + 32 + 4 * NMAX + tc * (step_child_stride(W) + PRED_STRIDE) + 3) & ~3;
+}
+// Children per tile: the most (at most 64) that four waves' LDS allows beside the tally and the program.
+__host__ __device__ constexpr int step_tile_children(int W) {
+  const int budget = (65536 / 4 - AUDIT_HEAD - PRED_MAX_WORDS) / STEP_WPB;
+  const int tc = (budget - step_wave_words(W, 0)) / (step_child_stride(W) + PRED_STRIDE);
+  return tc > 64 ? 64 : tc;
+}
+static_assert(step_tile_children(WMAX) >= 4, "the widest row's tile holds a few children");
+static_assert((AUDIT_HEAD + PRED_MAX_WORDS + STEP_WPB * step_wave_words(WMAX, step_tile_children(WMAX))) * 4 <= 65536 &&
+                  (AUDIT_HEAD + PRED_MAX_WORDS + STEP_WPB * step_wave_words(43, step_tile_children(43))) * 4 <= 65536,
+              "a block's LDS");
+
+// masks (may be null): the OR of the false-definition masks over each row's steps.
+template <int NS>
+__global__ void __launch_bounds__(64 * STEP_WPB)
+k_pred_step(Layout L, Ring cur, unsigned long long n, int tc, const uint32_t* __restrict__ prog, int nwords,
+            int* __restrict__ masks, AuditCounters* ctr) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int W = L.W, cs = step_child_stride(W);
+  uint32_t* const code = lds + AUDIT_HEAD;
+  uint32_t* const prow = code + PRED_MAX_WORDS + wave * step_wave_words(W, tc);
+  uint32_t* const pall = prow + even_words(W);
+  FP* const hsrv = reinterpret_cast<FP*>(pall + 32);
+  uint32_t* const stage = pall + 32 + 4 * NMAX;
+  int* const files = reinterpret_cast<int*>(stage + tc * cs);
+  for (int k = threadIdx.x; k < nwords; k += blockDim.x) code[k] = prog[k];
+  cover_zero(lds, AUDIT_HEAD);  // (its barrier also publishes the program)
+
+  unsigned int cnt[PRED_MAX_DEFS] = {};
+  unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
+  const int fixed = L.fam[F_RECEIVE];
+  for (unsigned long long s = (unsigned long long)blockIdx.x * wpb + wave; s < n;
+       s += (unsigned long long)gridDim.x * wpb) {
+    const FP pfp = load_parent<NS>(L, ring_row(cur, s, W), prow, pall, hsrv, lane);
+    const int nmsg = row_nmsg(L, prow);
+    const int ncand = fixed + 3 * nmsg;
+    int all = 0;
+    bool found = false;
+    for (int base = 0; base < ncand; base += 64) {
+      const int q = base + lane;
+      DeltaT<NS> d;
+      d.enabled = 0;
+      d.in_model = 0;
+      int inst = 0;
+      if (q < ncand) {
+        inst = candidate_inst(L, q, nmsg);
+        compute_delta<NS>(L, prow, inst, d);
+      }
+      const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
+      const unsigned long long m = __ballot(en);
+      const int nen = __popcll(m);
+      if (!nen) continue;
+      evaluated += nen;
+      const int rank = __popcll(m & ((1ull << lane) - 1ull));
+      const FP cfp = en ? fp_add(pfp, delta_fp<NS>(L, prow, d, d.srv >= 0 ? &hsrv[d.srv] : nullptr)) : FP{0, 0};
+      int bad = 0;
+      for (int b = 0; b < nen; b += tc) {
+        if (en && rank >= b && rank < b + tc) {
+          uint32_t* const child = stage + (rank - b) * cs;
+          materialize<NS>(L, prow, d, pall, cfp, child);
+          int err = 0;
+          bad = pred_eval_rows<NS, true>(L, (const uint32_t*)prow, (const uint32_t*)child, (const uint32_t*)code,
+                                         files + (rank - b) * PRED_STRIDE, &err);
+          if (err) {
+            atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
+            bad = 0;
+          }
+          if (step_stutters(prow, child)) bad = 0;  // (evaluated first, as [A]_vars: an error stays an error)
+        }
+        wave_sync();  // the next tile's lanes write the slots this tile's lanes read
+      }
+      const unsigned long long mb = __ballot(bad != 0);
+      if (mb) {
+        all |= audit_count(bad, cnt);
+        if (!found) {  // the row's least false instance: instances ascend with q
+          found = true;
+          const int fl = __builtin_ctzll(mb);
+          const unsigned long long key = step_key(s, __shfl(inst, fl), __shfl((int)d.in_model, fl), __shfl(bad, fl));
+          if (key < vkey) vkey = key;
+        }
+      }
+    }
+    if (masks && lane == 0) masks[s] = all;
+    wave_sync();
+  }
+  audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
+}
+
 namespace rtla {
+
+hipError_t launch_pred_step(const Layout& L, const Ring& cur, uint64_t n, const uint32_t* prog, int nwords,
+                            int* masks, AuditCounters* ctr, hipStream_t st) {
+  if (!n) return hipSuccess;
+  if (nwords < 1 || nwords > PRED_MAX_WORDS) return hipErrorInvalidValue;
+  const int tc = step_tile_children(L.W);
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + STEP_WPB - 1) / STEP_WPB, (uint64_t)device_cus() * 8);
+  const size_t lds = (size_t)(AUDIT_HEAD + PRED_MAX_WORDS + STEP_WPB * step_wave_words(L.W, tc)) * sizeof(uint32_t);
+  RTLA_DISPATCH_N(L, k_pred_step, dim3(grid), dim3(64 * STEP_WPB), lds, st, L, cur, (unsigned long long)n, tc, prog,
+                  nwords, masks, ctr);
+  return hipGetLastError();
+}
 
 hipError_t launch_pred(const Layout& L, const Ring& cur, uint64_t n, const uint32_t* prog, int nwords, int* masks,
                        AuditCounters* ctr, hipStream_t st) {

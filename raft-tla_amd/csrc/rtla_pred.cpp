@@ -53,12 +53,14 @@ struct Val {
   long lo = 0, hi = 0;  // T_INT: static interval
   uint64_t cost = 0;    // worst-case instructions
   int aux = 0;          // T_VSET: 1 = votesGranted, 0 = votesResponded (only the server index is emitted so far)
+  int row = 0;          // T_MSG / T_ELEC / T_MENTRIES / T_VSET / T_LOG / T_ELECTIONS: PRED_PRIME if of the primed row
 };
 
 struct Bound {
   std::string name;
   int type;
   long lo, hi;
+  int row = 0;  // T_MSG / T_ELEC: the row whose domain the variable ranges over (PRED_PRIME: the primed row)
 };
 
 struct Compiler {
@@ -68,8 +70,10 @@ struct Compiler {
   std::vector<uint32_t> code;
   int depth = 0, max_depth = 0, nest = 0;
   std::vector<Bound> scope;
+  const bool step;         // pred_compile's step: action definitions are compiled, state definitions skipped
+  bool in_action = false;  // inside [][ ... ]_vars: state variables may carry a prime
 
-  explicit Compiler(const Layout& l) : L(l) {}
+  Compiler(const Layout& l, bool step_) : L(l), step(step_) {}
 
   [[noreturn]] void fail(const Token& t, const std::string& msg) { throw Err{t.line, t.col, msg}; }
   const Token& cur() const { return toks[p]; }
@@ -89,6 +93,15 @@ struct Compiler {
     if (!is_ident(s)) fail(cur(), std::string("expected ") + s);
     take();
   }
+  // After a state variable's name: its prime, if any (PRED_PRIME), allowed inside [][ ... ]_vars only.
+  bool at_prime() const { return cur().k == K_UNSUPPORTED && cur().s == "'"; }
+  int prime() {
+    if (!at_prime()) return 0;
+    if (!in_action) fail(cur(), "''' is not supported");
+    take();
+    return PRED_PRIME;
+  }
+  static const char* row_name(int row) { return row ? "the primed row" : "the unprimed row"; }
 
   // ---- lexer
   void lex(const char* s, size_t n) {
@@ -302,12 +315,13 @@ struct Compiler {
       else if (is_ident("votesGranted")) which = 1;
       else fail(set, "expected votesResponded[i] or votesGranted[i] after \\in");
       take();
+      const int pr = prime();
       expect(K_LB, "[");
       const Token it = cur();
       Val i = expr();
       want(i, T_SERVER, it);
       expect(K_RB, "]");
-      emit(P_VIN, which, 0, -1);
+      emit(P_VIN, which | pr, 0, -1);
       Val r;
       r.cost = cadd(cadd(a.cost, i.cost), 1);
       (void)op;
@@ -320,6 +334,9 @@ struct Compiler {
       Val b = sum();
       if (a.type != b.type)
         fail(second, std::string("type error: ") + type_name(a.type) + " compared with " + type_name(b.type));
+      if ((a.type == T_MSG || a.type == T_ELEC) && a.row != b.row)
+        fail(second, std::string("type error: a ") + type_name(a.type) + " of " + row_name(a.row) +
+                         " compared with one of " + row_name(b.row));
       if (k != K_EQ && k != K_NE && a.type != T_INT)
         fail(op, std::string("type error: a ") + type_name(a.type) + " is compared only with = and #");
       emit(k == K_EQ ? P_EQ : k == K_NE ? P_NE : k == K_LT ? P_LT : k == K_LE ? P_LE : k == K_GT ? P_GT : P_GE, 0, 0,
@@ -417,12 +434,14 @@ struct Compiler {
         } else if (is_ident("DOMAIN")) {
           take();
           expect_ident("messages");
-          emit(P_DOM, PD_MESSAGES, 0, 2);
+          b.row = prime();
+          emit(P_DOM, PD_MESSAGES | b.row, 0, 2);
           b.type = T_MSG; b.lo = 0; b.hi = L.K - 1;
           trips = (uint64_t)L.K;
         } else if (is_ident("elections")) {
           take();
-          emit(P_DOM, PD_ELECTIONS, 0, 2);
+          b.row = prime();
+          emit(P_DOM, PD_ELECTIONS | b.row, 0, 2);
           b.type = T_ELEC; b.lo = 0; b.hi = L.E - 1;
           trips = (uint64_t)L.E;
         } else {
@@ -489,7 +508,7 @@ struct Compiler {
     return false;
   }
 
-  Val msg_field(const Token& f, uint64_t cost) {
+  Val msg_field(const Token& f, uint64_t cost, int row) {
     static const struct { const char* name; int field, type; } fields[] = {
         {"mtype", PM_TYPE, T_MTYPE}, {"mterm", PM_TERM, T_INT}, {"msource", PM_SOURCE, T_SERVER},
         {"mdest", PM_DEST, T_SERVER}, {"mlastLogTerm", PM_LASTLOGTERM, T_INT},
@@ -497,10 +516,14 @@ struct Compiler {
         {"mprevLogIndex", PM_PREVLOGINDEX, T_INT}, {"mprevLogTerm", PM_PREVLOGTERM, T_INT},
         {"mcommitIndex", PM_COMMITINDEX, T_INT}, {"msuccess", PM_SUCCESS, T_BOOL},
         {"mmatchIndex", PM_MATCHINDEX, T_INT}};
-    if (f.s == "mentries") return typed(T_MENTRIES, cost);  // (Len emits the read)
+    if (f.s == "mentries") {  // (Len emits the read)
+      Val r = typed(T_MENTRIES, cost);
+      r.row = row;
+      return r;
+    }
     for (const auto& e : fields)
       if (f.s == e.name) {
-        emit(P_MSG, e.field, 0, 0);
+        emit(P_MSG, e.field | row, 0, 0);
         Val r = typed(e.type, cadd(cost, 1));
         if (e.type == T_INT) {
           r.lo = e.field == PM_TERM ? 1 : 0;
@@ -513,6 +536,11 @@ struct Compiler {
   }
 
   Val prim() {
+    Val v = prim_unprimed();
+    if (in_action && at_prime()) fail(cur(), "only a state variable may carry a prime");
+    return v;
+  }
+  Val prim_unprimed() {
     Nest g(*this);
     const Token t = cur();
     switch (t.k) {
@@ -570,6 +598,9 @@ struct Compiler {
       Val b = expr();
       if (a.type != b.type)
         fail(et, std::string("type error: THEN is a ") + type_name(a.type) + ", ELSE a " + type_name(b.type));
+      if ((a.type == T_MSG || a.type == T_ELEC) && a.row != b.row)
+        fail(et, std::string("type error: THEN is a ") + type_name(a.type) + " of " + row_name(a.row) +
+                     ", ELSE one of " + row_name(b.row));
       patch(jmp);
       a.lo = std::min(a.lo, b.lo);
       a.hi = std::max(a.hi, b.hi);
@@ -597,11 +628,11 @@ struct Compiler {
       Val a = sum();
       expect(K_RP, ")");
       if (a.type == T_LOG) {
-        emit(P_LOGLEN, 0, 0, 0);
+        emit(P_LOGLEN, a.row, 0, 0);
         return ival(0, L.L + 1, cadd(a.cost, 1));
       }
       if (a.type == T_MENTRIES) {
-        emit(P_MSG, PM_NENTRIES, 0, 0);
+        emit(P_MSG, PM_NENTRIES | a.row, 0, 0);
         return ival(0, 1, cadd(a.cost, 1));
       }
       fail(at, std::string("type error: Len of a ") + type_name(a.type));
@@ -612,11 +643,11 @@ struct Compiler {
       Val a = sum();
       expect(K_RP, ")");
       if (a.type == T_VSET) {
-        emit(P_SRV, a.aux ? PS_NGRANTED : PS_NRESPONDED, 0, 0);
+        emit(P_SRV, (a.aux ? PS_NGRANTED : PS_NRESPONDED) | a.row, 0, 0);
         return ival(0, L.N, cadd(a.cost, 1));
       }
       if (a.type == T_ELECTIONS) {
-        emit(P_NELEC, 0, 0, 1);
+        emit(P_NELEC, a.row, 0, 1);
         return ival(0, L.E, 1);
       }
       fail(at, std::string("type error: Cardinality of a ") + type_name(a.type));
@@ -624,33 +655,46 @@ struct Compiler {
     if (s == "BagCardinality") {
       expect(K_LP, "(");
       expect_ident("messages");
+      const int pr = prime();
       expect(K_RP, ")");
-      emit(P_BAGCARD, 0, 0, 1);
+      emit(P_BAGCARD, pr, 0, 1);
       return ival(0, (long)L.K * (L.C + 1), 1);
     }
-    if (s == "elections") return typed(T_ELECTIONS, 0);
+    if (s == "elections") {
+      Val r = typed(T_ELECTIONS, 0);
+      r.row = prime();
+      return r;
+    }
     if (s == "currentTerm" || s == "state" || s == "votedFor" || s == "commitIndex") {
+      const int pr = prime();
       const uint64_t c = server_index();
       const int f = s == "currentTerm" ? PS_TERM : s == "state" ? PS_STATE : s == "votedFor" ? PS_VOTED : PS_COMMIT;
-      emit(P_SRV, f, 0, 0);
+      emit(P_SRV, f | pr, 0, 0);
       if (f == PS_TERM) return ival(1, L.T + 1, cadd(c, 1));
       if (f == PS_COMMIT) return ival(0, L.L, cadd(c, 1));
       return typed(f == PS_STATE ? T_STATE : T_SERVER, cadd(c, 1));
     }
     if (s == "votesResponded" || s == "votesGranted") {
+      const int pr = prime();
       Val r = typed(T_VSET, server_index());
       r.aux = s == "votesGranted";
+      r.row = pr;
       return r;
     }
     if (s == "log") {
+      const int pr = prime();
       uint64_t c = server_index();
-      if (cur().k != K_LB) return typed(T_LOG, c);
+      if (cur().k != K_LB) {
+        Val r = typed(T_LOG, c);
+        r.row = pr;
+        return r;
+      }
       take();
       const Token nt = cur();
       Val n = expr();
       want(n, T_INT, nt);
       expect(K_RB, "]");
-      emit(P_LOGENT, 0, 0, -1);
+      emit(P_LOGENT, pr, 0, -1);
       c = cadd(cadd(c, n.cost), 1);
       if (cur().k != K_DOT) return typed(T_ENTRY, c);
       take();
@@ -668,18 +712,22 @@ struct Compiler {
       fail(f, "expected .term or .value");
     }
     if (s == "nextIndex" || s == "matchIndex") {
+      const int pr = prime();
       uint64_t c = server_index();
       c = cadd(c, server_index());
-      emit(P_NM, s == "matchIndex", 0, -1);
+      emit(P_NM, (s == "matchIndex" ? 1 : 0) | pr, 0, -1);
       return s == "nextIndex" ? ival(1, L.L + 1, cadd(c, 1)) : ival(0, L.L, cadd(c, 1));
     }
     if (s == "messages") {
+      const int pr = prime();
       expect(K_LB, "[");
       const Token mt = cur();
       Val m = expr();
       want(m, T_MSG, mt);
+      if (m.row != pr)
+        fail(mt, std::string("type error: a message of ") + row_name(m.row) + " indexes the bag of " + row_name(pr));
       expect(K_RB, "]");
-      emit(P_MSG, PM_COUNT, 0, 0);
+      emit(P_MSG, PM_COUNT | pr, 0, 0);
       return ival(1, L.C + 1, cadd(m.cost, 1));
     }
     for (size_t k = scope.size(); k-- > 0;) {
@@ -688,15 +736,16 @@ struct Compiler {
       Val r = typed(scope[k].type, 1);
       r.lo = scope[k].lo;
       r.hi = scope[k].hi;
+      r.row = scope[k].row;
       if (cur().k != K_DOT) return r;
       take();
       const Token f = cur();
       if (f.k != K_IDENT) fail(f, "expected a field name");
       take();
-      if (r.type == T_MSG) return msg_field(f, 1);
+      if (r.type == T_MSG) return msg_field(f, 1, r.row);
       if (r.type == T_ELEC) {
-        if (f.s == "eterm") { emit(P_ELEC, 0, 0, 0); return ival(1, L.T, 2); }
-        if (f.s == "eleader") { emit(P_ELEC, 1, 0, 0); return typed(T_SERVER, 2); }
+        if (f.s == "eterm") { emit(P_ELEC, r.row, 0, 0); return ival(1, L.T, 2); }
+        if (f.s == "eleader") { emit(P_ELEC, 1 | r.row, 0, 0); return typed(T_SERVER, 2); }
         if (unsupported_name(f.s)) fail(f, "'" + f.s + "' is not supported");
         fail(f, "unknown election field '" + f.s + "'");
       }
@@ -723,6 +772,7 @@ struct Compiler {
       }
     }
     uint64_t steps = 1;  // P_HALT
+    std::vector<std::string> defined;  // every definition's name (a step set compiles the action definitions only)
     while (cur().k != K_EOF && cur().k != K_EQUALS) {
       const Token name = cur();
       if (name.k != K_IDENT) fail(name, "expected a definition (Name == expression)");
@@ -733,13 +783,38 @@ struct Compiler {
       for (const char* b : builtin)
         if (name.s == b) fail(name, "'" + name.s + "' is a built-in invariant's name");
       if (known_name(name.s)) fail(name, "'" + name.s + "' is reserved");
-      for (const std::string& n : out->names)
+      for (const std::string& n : defined)
         if (n == name.s) fail(name, "'" + name.s + "' is defined twice");
+      defined.push_back(name.s);
+      // Name == [][ expr ]_vars: an action definition, compiled by a step set only
+      const bool action = step && cur().k == K_LB && peek().k == K_RB && peek(2).k == K_LB;
+      if (step && !action) {  // a state definition of a step set's text: parsed, type-checked, not compiled
+        const size_t code0 = code.size();
+        const int depth0 = max_depth;
+        const Token bt = cur();
+        Val v = expr();
+        if (v.type != T_BOOL)
+          fail(bt, std::string("type error: a definition must be Boolean, this is a ") + type_name(v.type));
+        code.resize(code0);
+        depth = 0;
+        max_depth = depth0;
+        continue;
+      }
       if (out->names.size() >= (size_t)PRED_MAX_DEFS)
-        fail(name, "more than " + std::to_string(PRED_MAX_DEFS) + " definitions");
+        fail(name, "more than " + std::to_string(PRED_MAX_DEFS) + (step ? " action definitions" : " definitions"));
+      if (action) {
+        take(); take(); take();
+        in_action = true;
+      }
       const Token bt = cur();
       Val v = expr();
       if (v.type != T_BOOL) fail(bt, std::string("type error: a definition must be Boolean, this is a ") + type_name(v.type));
+      if (action) {
+        in_action = false;
+        expect(K_RB, "]_vars");
+        if (!is_ident("_vars")) fail(cur(), "expected _vars (the only subscript of an action definition)");
+        take();
+      }
       emit(P_DEFEND, (int)out->names.size(), 0, -1);
       steps = cadd(steps, cadd(v.cost, 1));
       if (steps > PRED_MAX_STEPS)
@@ -758,14 +833,16 @@ struct Compiler {
 
 }  // namespace
 
-bool pred_compile(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err) {
-  Compiler c(L);
+static bool compile_set(const Layout& L, const char* text, size_t len, bool step, rtla_pred* out, std::string* err) {
+  Compiler c(L, step);
   out->L = L;
+  out->step = step;
   out->names.clear();
   out->code.clear();
   try {
     c.lex(text, len);
     c.file(out);
+    if (step && out->names.empty()) throw Err{1, 1, "the text holds no action definition (Name == [][ expr ]_vars)"};
   } catch (const Err& e) {
     if (err) *err = std::to_string(e.line) + ":" + std::to_string(e.col) + ": " + e.msg;
     out->names.clear();
@@ -774,6 +851,13 @@ bool pred_compile(const Layout& L, const char* text, size_t len, rtla_pred* out,
   out->code = std::move(c.code);
   out->depth = c.max_depth;
   return true;
+}
+
+bool pred_compile(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err) {
+  return compile_set(L, text, len, false, out, err);
+}
+bool pred_compile_step(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err) {
+  return compile_set(L, text, len, true, out, err);
 }
 
 }  // namespace rtla

@@ -16,6 +16,9 @@
 // checked variable numbers, the stack depth and the step bound, and the
 // interpreter counts its steps all the same (PRED_MAX_STEPS).
 //
+// An action set (rtla_pred_compile_step) is the same bytecode over two rows, see
+// pred_eval_rows below.
+//
 // Evaluation errors (TLC's, never FALSE): a server index outside Server
 // (votedFor's Nil), log[i][n] with n outside 1..Len(log[i]), a per-type
 // message field read on a message of another type.
@@ -85,21 +88,39 @@ RTLA_HD int pred_field_type(int f) {
   return f < PM_LASTLOGTERM ? -1 : f < PM_VOTEGRANTED ? RVREQ : f < PM_PREVLOGINDEX ? RVRESP : f < PM_SUCCESS ? AEREQ : AERESP;
 }
 
-// Runs `prog` on one row.  file: PRED_FILE int32 words of this evaluation's own
-// (file[k] an lvalue).  Returns the mask of the definitions that are FALSE on
-// the row (bit k = definition k); *err = 1 on an evaluation error (the mask
-// then means nothing).
-template <int NS, class P, class Q, class F>
-RTLA_HD int pred_eval(const Layout& L, P row, Q prog, F file, int* err) {
+// An action program reads two rows, a step's state and
+// its successor: the instructions that read a row (P_DOM, P_SRV, P_VIN,
+// P_LOGLEN, P_LOGENT, P_NM, P_BAGCARD, P_NELEC, P_MSG, P_ELEC) read the primed
+// row when PRED_PRIME is set in their `a` field.  A state program never sets it.
+constexpr int PRED_PRIME = 128;
+
+// Runs `prog` on one row (STEP: on the step row -> row2).  file: PRED_FILE int32
+// words of this evaluation's own (file[k] an lvalue).  Returns the mask of the
+// definitions that are FALSE on the row (bit k = definition k); *err = 1 on an
+// evaluation error (the mask then means nothing).  Without STEP row2 is never
+// read and the code is the one-row interpreter's.
+template <int NS, bool STEP, class P, class Q, class F>
+RTLA_HD int pred_eval_rows(const Layout& L, P row1, P row2, Q prog, F file, int* err) {
   const int N = NS ? NS : L.N;
-  int nmsg = row_nmsg(L, row), nelec = row_nelec(L, row);
-  if (nmsg > L.K) nmsg = L.K;  // (a valid row's are within; no read past the row either way)
-  if (nelec > L.E) nelec = L.E;
+  int nmsg1 = row_nmsg(L, row1), nelec1 = row_nelec(L, row1);
+  if (nmsg1 > L.K) nmsg1 = L.K;  // (a valid row's are within; no read past the row either way)
+  if (nelec1 > L.E) nelec1 = L.E;
+  int nmsg2 = 0, nelec2 = 0;
+  if (STEP) {
+    nmsg2 = row_nmsg(L, row2);
+    nelec2 = row_nelec(L, row2);
+    if (nmsg2 > L.K) nmsg2 = L.K;
+    if (nelec2 > L.E) nelec2 = L.E;
+  }
   int mask = 0, bad = 0, pc = 0, sp = PRED_VARS;  // sp: the next free word of the file
   for (uint32_t steps = 0;; steps++) {
     if (steps > PRED_MAX_STEPS) { bad = 1; break; }
     const uint32_t w = prog[pc++];
-    const int op = pred_op(w), a = pred_a(w);
+    const int op = pred_op(w);
+    const bool primed = STEP && (pred_a(w) & PRED_PRIME);
+    const int a = STEP ? pred_a(w) & (PRED_PRIME - 1) : pred_a(w);
+    const P row = primed ? row2 : row1;
+    const int nmsg = primed ? nmsg2 : nmsg1, nelec = primed ? nelec2 : nelec1;
     if (op == P_HALT) break;
     switch (op) {
       case P_PUSHI: file[sp++] = pred_imm(w); break;
@@ -244,6 +265,10 @@ RTLA_HD int pred_eval(const Layout& L, P row, Q prog, F file, int* err) {
   }
   *err = bad;
   return mask;
+}
+template <int NS, class P, class Q, class F>
+RTLA_HD int pred_eval(const Layout& L, P row, Q prog, F file, int* err) {
+  return pred_eval_rows<NS, false>(L, row, row, prog, file, err);
 }
 
 }  // namespace rtla

@@ -13,11 +13,15 @@ struct rtla_pred {
   std::vector<std::string> names;  // definition k = bit k
   uint64_t steps = 0;              // worst-case instructions per row
   int depth = 0;                   // operand depth reached
+  bool step = false;               // an action set: the program reads a step's two rows (pred_eval_rows)
 };
 
 namespace rtla {
 
 // Compiles `text` (len bytes) for layout L.  false: *err = "line:col: message".
 bool pred_compile(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err);
+// The same for the text's action definitions `Name == [][ expr ]_vars`; its state
+// definitions are parsed, type-checked and skipped.  A text without an action definition is an error.
+bool pred_compile_step(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err);
 
 }  // namespace rtla

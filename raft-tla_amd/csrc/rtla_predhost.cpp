@@ -8,15 +8,16 @@
 
 #include "rtla_ctx.h"
 #include "rtla_predc.h"
+#include "rtla_step.h"
 
-extern "C" int rtla_pred_compile(const rtla_cfg* c, const char* text, rtla_pred** out, char* err, size_t errcap) {
+static int compile_abi(const rtla_cfg* c, const char* text, bool step, rtla_pred** out, char* err, size_t errcap) {
   if (err && errcap) err[0] = 0;
   if (!text || !out) return RTLA_E_ARG;
   *out = nullptr;
   CFG_LAYOUT(L, c);
   rtla_pred* p = new rtla_pred;
   std::string msg;
-  if (!pred_compile(L, text, strlen(text), p, &msg)) {
+  if (!(step ? pred_compile_step : pred_compile)(L, text, strlen(text), p, &msg)) {
     delete p;
     if (err && errcap) snprintf(err, errcap, "%s", msg.c_str());
     return RTLA_E_ARG;
@@ -24,6 +25,17 @@ extern "C" int rtla_pred_compile(const rtla_cfg* c, const char* text, rtla_pred*
   *out = p;
   return RTLA_OK;
 }
+
+extern "C" int rtla_pred_compile(const rtla_cfg* c, const char* text, rtla_pred** out, char* err, size_t errcap) {
+  return compile_abi(c, text, false, out, err, errcap);
+}
+
+extern "C" int rtla_pred_compile_step(const rtla_cfg* c, const char* text, rtla_pred** out, char* err,
+                                      size_t errcap) {
+  return compile_abi(c, text, true, out, err, errcap);
+}
+
+extern "C" int rtla_pred_is_step(const rtla_pred* p) { return p ? (int)p->step : RTLA_E_ARG; }
 
 extern "C" void rtla_pred_free(rtla_pred* p) { delete p; }
 
@@ -42,34 +54,24 @@ static bool pred_bound_to(const rtla_pred* p, const Layout& L) {
   return q.N == L.N && q.V == L.V && q.T == L.T && q.L == L.L && q.C == L.C && q.M == L.M && q.K == L.K &&
          q.E == L.E && q.W == L.W;
 }
-// The layout of *c, if `p` was compiled for it.
-static int pred_layout(const rtla_cfg* c, const rtla_pred* p, Layout* L) {
+// The layout of *c, if `p` was compiled for it and is of the kind the call takes (step: an action set).
+static int pred_layout(const rtla_cfg* c, const rtla_pred* p, bool step, Layout* L) {
   if (int r = layout_from_cfg(c, L)) return r;
-  return p && pred_bound_to(p, *L) ? RTLA_OK : RTLA_E_ARG;
+  return p && p->step == step && pred_bound_to(p, *L) ? RTLA_OK : RTLA_E_ARG;
 }
 
-extern "C" int rtla_pred_replay(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int threads,
-                                int32_t* masks, uint64_t* counts) {
-  Layout L;
-  if (int r = pred_layout(c, p, &L)) return r;
-  if (threads < 0 || !masks || (n && !rows)) return RTLA_E_ARG;
+// The host replay of both kinds: row(k, tally) evaluates row k into the thread's tally and returns its mask.
+template <class F>
+static int replay_rows(size_t n, int threads, int32_t* masks, uint64_t* counts, uint64_t* evaluated, F row) {
   const int nt = (int)std::min<size_t>((size_t)std::min(text_threads(threads), 16), std::max<size_t>(1, n / 256));
   std::vector<AuditCounters> part((size_t)nt, audit_zero());
   std::atomic<size_t> next{0};
   auto work = [&](int t) {
     AuditCounters& tl = part[(size_t)t];
-    int file[PRED_FILE];
     for (;;) {
       const size_t b = next.fetch_add(256);
       if (b >= n) break;
-      for (size_t k = b; k < std::min(n, b + 256); k++) {
-        int err = 0;
-        const int bad = pred_eval<0>(L, rows + k * (size_t)L.W, p->code.data(), file, &err);
-        if (err) tl.flags |= FLAG_SPEC_ERROR;
-        masks[k] = err ? 0 : bad;
-        if (!err)
-          for (int d = 0; d < PRED_MAX_DEFS; d++) tl.counts[d] += bad >> d & 1;
-      }
+      for (size_t k = b; k < std::min(n, b + 256); k++) masks[k] = row(k, tl);
     }
   };
   std::vector<std::thread> pool;
@@ -77,21 +79,56 @@ extern "C" int rtla_pred_replay(const rtla_cfg* c, const rtla_pred* p, const uin
   work(0);
   for (auto& th : pool) th.join();
   int flags = 0;
-  uint64_t sum[AUDIT_COUNTS] = {};
+  uint64_t sum[AUDIT_COUNTS] = {}, ev = 0;
   for (const AuditCounters& q : part) {
     flags |= q.flags;
+    ev += q.evaluated;
     for (int k = 0; k < AUDIT_COUNTS; k++) sum[k] += q.counts[k];
   }
   if (flags) return flags_to_status(flags);
   if (counts)
     for (int k = 0; k < AUDIT_COUNTS; k++) counts[k] = sum[k];
+  if (evaluated) *evaluated = ev;
   return RTLA_OK;
 }
 
-extern "C" int rtla_pred_batch(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int32_t* masks,
-                               uint64_t* counts) {
+extern "C" int rtla_pred_replay(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int threads,
+                                int32_t* masks, uint64_t* counts) {
   Layout L;
-  if (int r = pred_layout(c, p, &L)) return r;
+  if (int r = pred_layout(c, p, false, &L)) return r;
+  if (threads < 0 || !masks || (n && !rows)) return RTLA_E_ARG;
+  return replay_rows(n, threads, masks, counts, nullptr, [&](size_t k, AuditCounters& tl) {
+    int file[PRED_FILE];
+    int err = 0;
+    const int bad = pred_eval<0>(L, rows + k * (size_t)L.W, p->code.data(), file, &err);
+    if (err) {
+      tl.flags |= FLAG_SPEC_ERROR;
+      return 0;
+    }
+    for (int d = 0; d < PRED_MAX_DEFS; d++) tl.counts[d] += bad >> d & 1;
+    return bad;
+  });
+}
+
+extern "C" int rtla_pred_step_replay(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n,
+                                     int threads, int32_t* masks, uint64_t* counts, uint64_t* evaluated) {
+  Layout L;
+  if (int r = pred_layout(c, p, true, &L)) return r;
+  if (threads < 0 || !masks || (n && !rows)) return RTLA_E_ARG;
+  return replay_rows(n, threads, masks, counts, evaluated, [&](size_t k, AuditCounters& tl) {
+    return dispatch_n(L, [&](auto ns) {
+      return step_row_serial<decltype(ns)::value>(L, rows + k * (size_t)L.W, k, p->code.data(), tl);
+    });
+  });
+}
+
+// The kernel of a set's kind (rtla_kpred.hip).
+static auto pred_launcher(const rtla_pred* p) { return p->step ? launch_pred_step : launch_pred; }
+
+static int pred_batch(const rtla_cfg* c, const rtla_pred* p, bool step, const uint32_t* rows, size_t n,
+                      int32_t* masks, uint64_t* counts, uint64_t* evaluated) {
+  Layout L;
+  if (int r = pred_layout(c, p, step, &L)) return r;
   if (!masks || (n && !rows)) return RTLA_E_ARG;
   uint32_t* d_prog = nullptr;
   const size_t bytes = p->code.size() * sizeof(uint32_t);
@@ -99,24 +136,43 @@ extern "C" int rtla_pred_batch(const rtla_cfg* c, const rtla_pred* p, const uint
   int rc = RTLA_E_HIP;
   if (hipMemcpy(d_prog, p->code.data(), bytes, hipMemcpyHostToDevice) == hipSuccess)
     rc = audit_batch(L, rows, n, [&](const Ring& cur, uint64_t nr, int* m, AuditCounters* ctr, hipStream_t st) {
-      return launch_pred(L, cur, nr, d_prog, (int)p->code.size(), m, ctr, st);
-    }, masks, counts);
+      return pred_launcher(p)(L, cur, nr, d_prog, (int)p->code.size(), m, ctr, st);
+    }, masks, counts, evaluated);
   (void)hipFree(d_prog);
   return rc;
 }
 
-extern "C" int rtla_pred_frontier(rtla_ctx* x, const rtla_pred* p, rtla_audit_stats* out) {
+extern "C" int rtla_pred_batch(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int32_t* masks,
+                               uint64_t* counts) {
+  return pred_batch(c, p, false, rows, n, masks, counts, nullptr);
+}
+
+extern "C" int rtla_pred_step_batch(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n,
+                                    int32_t* masks, uint64_t* counts, uint64_t* evaluated) {
+  return pred_batch(c, p, true, rows, n, masks, counts, evaluated);
+}
+
+static int pred_frontier(rtla_ctx* x, const rtla_pred* p, bool step, rtla_audit_stats* out) {
   if (!x || !p) return RTLA_E_ARG;
   if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
       x->sh[0].n_cur == 0)
     return RTLA_E_STATE;
   const Layout L = x->L;
-  if (!pred_bound_to(p, L)) return RTLA_E_ARG;
+  if (p->step != step || !pred_bound_to(p, L)) return RTLA_E_ARG;
   HIPCHK(hipSetDevice(x->device));
   AuditState& a = x->audit;
   if (!a.prog) HIPCHK(hipMalloc((void**)&a.prog, PRED_MAX_WORDS * sizeof(uint32_t)));
   HIPCHK(hipMemcpyAsync(a.prog, p->code.data(), p->code.size() * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
-  return audit_frontier(x, 0, true, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
-    return launch_pred(L, cur, n, a.prog, (int)p->code.size(), m, ctr, st);
-  }, out);
+  return audit_frontier(x, step, step ? AUDIT_PRED_STEP : AUDIT_PRED_STATE,
+                        [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
+                          return pred_launcher(p)(L, cur, n, a.prog, (int)p->code.size(), m, ctr, st);
+                        }, out);
+}
+
+extern "C" int rtla_pred_frontier(rtla_ctx* x, const rtla_pred* p, rtla_audit_stats* out) {
+  return pred_frontier(x, p, false, out);
+}
+
+extern "C" int rtla_pred_step_frontier(rtla_ctx* x, const rtla_pred* p, rtla_audit_stats* out) {
+  return pred_frontier(x, p, true, out);
 }

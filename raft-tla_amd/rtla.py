@@ -151,6 +151,13 @@ def _load():
                                        P(C.c_uint64)]),
         "rtla_pred_batch": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, P(C.c_int32), P(C.c_uint64)]),
         "rtla_pred_frontier": (C.c_int, [C.c_void_p, C.c_void_p, P(_AuditStats)]),
+        "rtla_pred_compile_step": (C.c_int, [P(_Cfg), C.c_char_p, P(C.c_void_p), C.c_char_p, C.c_size_t]),
+        "rtla_pred_is_step": (C.c_int, [C.c_void_p]),
+        "rtla_pred_step_replay": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, C.c_int, P(C.c_int32),
+                                            P(C.c_uint64), P(C.c_uint64)]),
+        "rtla_pred_step_batch": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, P(C.c_int32),
+                                           P(C.c_uint64), P(C.c_uint64)]),
+        "rtla_pred_step_frontier": (C.c_int, [C.c_void_p, C.c_void_p, P(_AuditStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -171,7 +178,9 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_level_orbit_hash", "rtla_orbit_text", "rtla_probe_bench3", "rtla_random_texts",
             "rtla_frontier_rows", "rtla_simulate", "rtla_sim_replay", "rtla_sim_walk", "rtla_check_batch",
             "rtla_check_replay", "rtla_check_frontier", "rtla_fpset_probe", "rtla_pred_compile", "rtla_pred_free",
-            "rtla_pred_count", "rtla_pred_name", "rtla_pred_replay", "rtla_pred_batch", "rtla_pred_frontier"]
+            "rtla_pred_count", "rtla_pred_name", "rtla_pred_replay", "rtla_pred_batch", "rtla_pred_frontier",
+            "rtla_pred_compile_step", "rtla_pred_is_step", "rtla_pred_step_replay", "rtla_pred_step_batch",
+            "rtla_pred_step_frontier"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -385,17 +394,26 @@ class Predicates:
     (specs/MCPredicates.tla), compiled for cfg's row
     layout.  A syntax, type or bound error raises RtlaError(E_ARG) whose
     message starts with line:col.  Use as a context manager, or leave it to
-    the garbage collector."""
+    the garbage collector.
 
-    def __init__(self, cfg: Config, text: str):
+    step=True (or the Actions subclass) compiles the text's action definitions
+    `Name == [][expr]_vars` instead (rtla_pred_compile_step; DESIGN.md section
+    14, specs/MCActions.tla): `names` are the action definitions, the state
+    definitions of the same text are checked and skipped.  A set knows its
+    kind: a state set goes to pred_replay / pred_batch / audit_predicates, a
+    step set to pred_step_replay / pred_step_batch / audit_steps."""
+
+    def __init__(self, cfg: Config, text: str, step: bool = False):
         self.cfg = cfg
+        self.step = bool(step)
         self._h = None
         cc = cfg.c()
         h = C.c_void_p()
         err = C.create_string_buffer(512)
-        rc = _lib.rtla_pred_compile(C.byref(cc), text.encode(), C.byref(h), err, len(err))
+        what = "rtla_pred_compile_step" if step else "rtla_pred_compile"
+        rc = getattr(_lib, what)(C.byref(cc), text.encode(), C.byref(h), err, len(err))
         if rc < 0:
-            raise RtlaError(rc, "rtla_pred_compile: " + err.value.decode() if err.value else "rtla_pred_compile")
+            raise RtlaError(rc, what + ": " + err.value.decode() if err.value else what)
         self._h = h
         buf = C.create_string_buffer(256)
         self.names: List[str] = []
@@ -425,15 +443,24 @@ class Predicates:
             pass
 
 
-def _pred_rows(fn, what: str, preds: Predicates, rows, *extra):
+class Actions(Predicates):
+    """A compiled set of action properties: Predicates(cfg, text, step=True)."""
+
+    def __init__(self, cfg: Config, text: str):
+        super().__init__(cfg, text, step=True)
+
+
+def _pred_rows(fn, what: str, preds: Predicates, rows, *extra, steps: bool = False):
     cc = preds.cfg.c()
     flat, n = _flat_rows(rows, row_words(preds.cfg))
     masks = (C.c_int32 * max(1, n))()
     counts = (C.c_uint64 * 8)()
-    rc = fn(C.byref(cc), preds._h, flat, n, *extra, masks, counts)
+    evaluated = C.c_uint64(0)
+    rc = fn(C.byref(cc), preds._h, flat, n, *extra, masks, counts, *([C.byref(evaluated)] if steps else []))
     if rc < 0:
         raise RtlaError(rc, what, CAP_SPEC_ERROR if rc == E_SPEC else 0)
-    return list(masks[:n]), {nm: counts[k] for k, nm in enumerate(preds.names)}
+    res = list(masks[:n]), {nm: counts[k] for k, nm in enumerate(preds.names)}
+    return res + (evaluated.value,) if steps else res
 
 
 def pred_replay(preds: Predicates, rows, threads: int = 0):
@@ -447,6 +474,21 @@ def pred_replay(preds: Predicates, rows, threads: int = 0):
 def pred_batch(preds: Predicates, rows):
     """The same on the GPU (rtla_pred_batch: rtla_kpred.hip)."""
     return _pred_rows(_lib.rtla_pred_batch, "rtla_pred_batch", preds, rows)
+
+
+def pred_step_replay(actions: Predicates, rows, threads: int = 0):
+    """An action set evaluated on the host (rtla_pred_step_replay) on every step
+    (rows[k], enabled successor): (masks, counts, evaluated) -- masks[k] the OR
+    over the steps out of rows[k] of the definitions false on the step,
+    counts[name] the steps on which it is false, evaluated the steps.  A
+    stuttering step satisfies every definition; an evaluation error on any
+    step raises RtlaError(E_SPEC)."""
+    return _pred_rows(_lib.rtla_pred_step_replay, "rtla_pred_step_replay", actions, rows, threads, steps=True)
+
+
+def pred_step_batch(actions: Predicates, rows):
+    """The same on the GPU (rtla_pred_step_batch: k_pred_step, rtla_kpred.hip)."""
+    return _pred_rows(_lib.rtla_pred_step_batch, "rtla_pred_step_batch", actions, rows, steps=True)
 
 
 def row_words(cfg: Config) -> int:
@@ -696,14 +738,20 @@ class Checker:
         self._rec(st)
         return self.status
 
-    def run(self, max_levels: int = 100000, predicates: Optional[Predicates] = None) -> int:
+    def run(self, max_levels: int = 100000, predicates: Optional[Predicates] = None,
+            actions: Optional[Predicates] = None) -> int:
         """BFS until the search ends, a violation or max_levels.  predicates: a
         set audited on every level right after it is produced, Init's included
         (audit_predicates); the run stops with VIOLATION at the first level that
-        holds a state on which a definition is false."""
+        holds a state on which a definition is false.  actions: a step set
+        checked after them on the steps out of every level (audit_steps), before
+        the next step(): every step out of every reachable in-model state is
+        checked, and the run stops at the first level with a false step."""
         def audited() -> int:
-            if predicates is not None and self.status == OK and self.levels[-1].new > 0:
-                if self.audit_predicates(predicates).status == VIOLATION:
+            if self.status == OK and self.levels[-1].new > 0:  # (the last, empty level is skipped)
+                if predicates is not None and self.audit_predicates(predicates).status == VIOLATION:
+                    self.status = VIOLATION
+                elif actions is not None and self.audit_steps(actions).status == VIOLATION:
                     self.status = VIOLATION
             return self.status
 
@@ -864,11 +912,23 @@ class Checker:
         violation name definitions; otherwise as audit(): the BFS is left
         untouched, and after a VIOLATION result violation() and trace() give the
         counterexample, until the next step, audit or simulation."""
+        return self._audit_set(_lib.rtla_pred_frontier, "rtla_pred_frontier", preds)
+
+    def audit_steps(self, actions: Predicates) -> AuditResult:
+        """Evaluate a compiled action set on every step out of the states of
+        the level last produced, in place on the GPU (rtla_pred_step_frontier):
+        audited is the rows, evaluated the steps, counts[name] the steps on
+        which it is false.  After a VIOLATION result, viol_index / viol_inst
+        name the least (row, action instance) with a false definition, and
+        trace() ends in that step: the row, then its successor."""
+        return self._audit_set(_lib.rtla_pred_step_frontier, "rtla_pred_step_frontier", actions)
+
+    def _audit_set(self, fn, what: str, preds: Predicates) -> AuditResult:
         st = _AuditStats()
         self._pred_viol = None
-        rc = _lib.rtla_pred_frontier(self._h, preds._h, C.byref(st))
+        rc = fn(self._h, preds._h, C.byref(st))
         if rc < 0:
-            raise RtlaError(rc, "rtla_pred_frontier", st.flags)
+            raise RtlaError(rc, what, st.flags)
         res = AuditResult(status=rc, audited=st.audited, evaluated=st.evaluated, kernel_ms=st.kernel_ms,
                           row_bytes=st.row_bytes, counts={nm: st.counts[k] for k, nm in enumerate(preds.names)})
         if rc == VIOLATION:
@@ -885,12 +945,14 @@ class Checker:
         return {COVER_NAMES[k]: (g[k], d[k]) for k in range(n)}
 
 
-def check(cfg: Config, trace: bool = True, predicates: Optional[Predicates] = None) -> Result:
+def check(cfg: Config, trace: bool = True, predicates: Optional[Predicates] = None,
+          actions: Optional[Predicates] = None) -> Result:
     """Exhaustive BFS of the model (TLC `-workers N` breadth-first mode).
     predicates: user-defined invariants checked on every level (Checker.run);
+    actions: action properties checked on the steps out of every level;
     Result.violation then names the false definitions."""
     with Checker(cfg) as ck:
-        st = ck.run(predicates=predicates)
+        st = ck.run(predicates=predicates, actions=actions)
         res = Result(distinct=ck.distinct, generated=ck.generated, levels=list(ck.levels))
         res.depth = sum(1 for lv in ck.levels if lv.new > 0)
         res.seconds = sum(lv.seconds for lv in ck.levels)

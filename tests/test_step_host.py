@@ -1,0 +1,386 @@
+"""CPU tests of the action properties: the step compiler
+(rtla_pred_compile_step) and the host replay (rtla_pred_step_replay).  No kernel
+is launched.
+
+The oracle is (state, successor) pairs from raft_values.next_states on states
+parsed from rtla.state_text, as tests/test_safety_host.py's successor test
+uses them; each action definition is paired with a Python function of (cfg, s,
+t) written from the TLA+ text alone.  The Python side skips t == s."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import hostmodel
+import raft_values as rv
+import rtla
+import tla_text
+from test_safety_host import SHAPES, SUCC_ROWS
+from test_safety_host import setup as make_case
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MCACTIONS = open(os.path.join(ROOT, "specs", "MCActions.tla")).read()
+LAWS = ["LeaderAppendOnly", "TermsNeverDecrease", "OneVotePerTerm", "BagChangesByOne", "ElectionsGrow"]
+WITNESSES = ["LeadersStay", "CommitNeverDecreases", "TermsFrozen"]
+
+
+def _v(s, name):
+    return s[rv.IX[name]]
+
+
+def _srv(c):
+    return range(c.n_server)
+
+
+def _bag(s):
+    return sum(n for _, n in _v(s, "messages").items())
+
+
+def _pairs(c):
+    return [(i, j) for i in _srv(c) for j in _srv(c)]
+
+
+def _same(name):
+    return lambda c, s, t: all(_v(t, name)[i] == _v(s, name)[i] for i in _srv(c))
+
+
+def _act(body):
+    return "[][ %s ]_vars" % body
+
+
+# ---- the definitions of specs/MCActions.tla in Python, from the TLA+ text
+
+def leader_append_only(c, s, t):
+    for i in _srv(c):
+        if (_v(s, "state")[i] == rv.LEADER and _v(t, "state")[i] == rv.LEADER
+                and _v(t, "currentTerm")[i] == _v(s, "currentTerm")[i]):
+            old, new = _v(s, "log")[i], _v(t, "log")[i]
+            if not (len(new) >= len(old) and all(new[n] == old[n] for n in range(len(old)))):
+                return False
+    return True
+
+
+MC_PY = {
+    "LeaderAppendOnly": leader_append_only,
+    "TermsNeverDecrease": lambda c, s, t: all(_v(t, "currentTerm")[i] >= _v(s, "currentTerm")[i] for i in _srv(c)),
+    "OneVotePerTerm": lambda c, s, t: all(
+        not (_v(t, "currentTerm")[i] == _v(s, "currentTerm")[i] and _v(s, "votedFor")[i] != rv.NIL)
+        or _v(t, "votedFor")[i] == _v(s, "votedFor")[i] for i in _srv(c)),
+    "BagChangesByOne": lambda c, s, t: _bag(t) <= _bag(s) + 1 and _bag(s) <= _bag(t) + 1,
+    "ElectionsGrow": lambda c, s, t: len(_v(s, "elections")) <= len(_v(t, "elections")) <= len(_v(s, "elections")) + 1,
+    "LeadersStay": lambda c, s, t: all(_v(s, "state")[i] != rv.LEADER or _v(t, "state")[i] == rv.LEADER
+                                       for i in _srv(c)),
+    "CommitNeverDecreases": lambda c, s, t: all(_v(t, "commitIndex")[i] >= _v(s, "commitIndex")[i] for i in _srv(c)),
+    "TermsFrozen": _same("currentTerm"),
+}
+
+# ---- field probes: action predicates that are no laws (name, text, the same in Python)
+
+PROBES = [
+    ("RolesKept", r"\A i \in Server : state'[i] = state[i]", _same("state")),
+    ("VotedForKept", r"\A i \in Server : votedFor'[i] = votedFor[i]", _same("votedFor")),
+    ("CommitKept", r"\A i \in Server : commitIndex'[i] = commitIndex[i]", _same("commitIndex")),
+    ("LogsKept", r"\A i \in Server : Len(log'[i]) = Len(log[i]) /\ \A n \in 1..Len(log[i]) : log'[i][n] = log[i][n]",
+     _same("log")),
+    ("NextIndexKept", r"\A i, j \in Server : nextIndex'[i][j] = nextIndex[i][j]",
+     lambda c, s, t: all(_v(t, "nextIndex")[i][j] == _v(s, "nextIndex")[i][j] for i, j in _pairs(c))),
+    ("MatchIndexNeverDecreases", r"\A i, j \in Server : matchIndex'[i][j] >= matchIndex[i][j]",
+     lambda c, s, t: all(_v(t, "matchIndex")[i][j] >= _v(s, "matchIndex")[i][j] for i, j in _pairs(c))),
+    ("VotesGrantedKept", r"\A i, j \in Server : j \in votesGranted[i] => j \in votesGranted'[i]",
+     lambda c, s, t: all(j not in _v(s, "votesGranted")[i] or j in _v(t, "votesGranted")[i] for i, j in _pairs(c))),
+    ("VotesRespondedKept", r"\A i \in Server : Cardinality(votesResponded'[i]) = Cardinality(votesResponded[i])",
+     lambda c, s, t: all(len(_v(t, "votesResponded")[i]) == len(_v(s, "votesResponded")[i]) for i in _srv(c))),
+    ("BagNeverGrows", r"BagCardinality(messages') <= BagCardinality(messages)",
+     lambda c, s, t: _bag(t) <= _bag(s)),
+    ("NewBagWithinOldDestTerm", r"\A m \in DOMAIN messages' : m.mterm <= currentTerm[m.mdest]",
+     lambda c, s, t: all(m["mterm"] <= _v(s, "currentTerm")[m["mdest"]] for m, _ in _v(t, "messages").items())),
+    ("NewBagSingleCopies", r"\A m \in DOMAIN messages' : messages'[m] = 1",
+     lambda c, s, t: all(n == 1 for _, n in _v(t, "messages").items())),
+    ("NewElectionsLeaderStillLeads",
+     r"\A e \in elections' : state'[e.eleader] = Leader /\ currentTerm'[e.eleader] = e.eterm",
+     lambda c, s, t: all(_v(t, "state")[e["eleader"]] == rv.LEADER and _v(t, "currentTerm")[e["eleader"]] == e["eterm"]
+                         for e in _v(t, "elections"))),
+    ("TermsFrozen", r"\A i \in Server : currentTerm'[i] = currentTerm[i]", MC_PY["TermsFrozen"]),
+    ("LeadersStay", r"\A i \in Server : state[i] = Leader => state'[i] = Leader", MC_PY["LeadersStay"]),
+    ("CommitNeverDecreases", r"\A i \in Server : commitIndex'[i] >= commitIndex[i]", MC_PY["CommitNeverDecreases"]),
+]
+PROBE_SETS = [PROBES[:8], PROBES[8:]]  # at most 8 definitions a set
+FRACTION = {}  # name -> the fraction of evaluated steps on which it is false, per shape
+
+
+def probe_text(group):
+    return "\n".join("%s == %s" % (name, _act(src)) for name, src, _ in group)
+
+
+def python_side(vc, states, named):
+    """(masks, counts, evaluated) of the definitions `named` [(name, fn)] over every step out of `states`."""
+    masks, counts, evaluated = [], dict.fromkeys([n for n, _ in named], 0), 0
+    for s in states:
+        acc = 0
+        for _, t in rv.next_states(vc, s):
+            evaluated += 1
+            if t == s:
+                continue
+            for k, (name, fn) in enumerate(named):
+                if not fn(vc, s, t):
+                    acc |= 1 << k
+                    counts[name] += 1
+        masks.append(acc)
+    return masks, counts, evaluated
+
+
+@pytest.fixture(scope="module", params=SHAPES, ids=lambda p: "n%d" % p[0][0])
+def case(request):
+    cfg, vc, rows, states = make_case(*request.param)
+    return cfg, vc, rows[:SUCC_ROWS], states[:SUCC_ROWS]
+
+
+def test_probes_match_the_python_functions_pair_for_pair(case):
+    cfg, vc, rows, states = case
+    for group in PROBE_SETS:
+        named = [(name, fn) for name, _, fn in group]
+        want = python_side(vc, states, named)
+        with rtla.Actions(cfg, probe_text(group)) as acts:
+            assert acts.names == [name for name, _ in named] and acts.step
+            assert rtla.pred_step_replay(acts, rows) == want
+        for name, _ in named:
+            FRACTION.setdefault(name, []).append(want[1][name] / want[2])
+    assert want[2] in (4214, 5168, 7802)  # the three shapes' successors
+
+
+def test_probes_take_both_values():
+    """From the Python side alone: every probe is false on >= 2 % and true on
+    >= 2 % of the evaluated steps of at least one shape."""
+    assert len(PROBES) >= 15
+    for name, _, _ in PROBES:
+        fr = FRACTION[name]
+        assert len(fr) == len(SHAPES) and any(0.02 <= f <= 0.98 for f in fr), (name, fr)
+
+
+def test_the_laws_hold_on_random_rows(case):
+    cfg, vc, rows, states = case
+    with rtla.Actions(cfg, MCACTIONS) as acts:
+        assert acts.names == LAWS + WITNESSES
+        masks, counts, evaluated = rtla.pred_step_replay(acts, rows)
+    want = python_side(vc, states, [(n, MC_PY[n]) for n in acts.names])
+    assert (masks, counts, evaluated) == want
+    assert [counts[n] for n in LAWS] == [0] * 5 and all(counts[n] > 0 for n in WITNESSES)
+
+
+# ---- the whole model n2_v1_t2_l1_m1, level by level
+
+MODEL = (2, 1, 2, 1, 1, 1)
+
+
+@pytest.fixture(scope="module")
+def model_levels():
+    """The BFS levels of MODEL as rows, by host expansion (tests/hostmodel.py: rtla_model.h compiled for
+    the host), and as value-oracle states parsed from their text."""
+    n, v, t, l, c, m = MODEL
+    cfg, vc = rtla.Config(n, v, t, l, c, m, ()), rv.Cfg(n, v, t, l, c, (), m)
+    words = rtla.row_words(cfg)
+    level, seen, levels = [rtla.init_row(cfg)], None, []
+    seen = {tuple(level[0])}
+    while level:
+        levels.append((level, [tla_text.parse_state(vc, rtla.state_text(cfg, r)) for r in level]))
+        nxt = []
+        for _, _, _, in_model, row in hostmodel.expand(cfg, level, words):
+            if in_model and tuple(row) not in seen:
+                seen.add(tuple(row))
+                nxt.append(row)
+        level = nxt
+    return cfg, vc, levels
+
+
+def test_whole_model_level_by_level(model_levels):
+    cfg, vc, levels = model_levels
+    ref = rv.bfs(vc)
+    assert [len(rows) for rows, _ in levels] == [new for new, _ in ref.levels if new] and len(levels) == 28
+    first_false = {}
+    with rtla.Actions(cfg, MCACTIONS) as acts:
+        named = [(n, MC_PY[n]) for n in acts.names]
+        for k, (rows, states) in enumerate(levels, start=1):
+            masks, counts, evaluated = rtla.pred_step_replay(acts, rows)
+            want = python_side(vc, states, named)
+            assert (masks, counts, evaluated) == want, k
+            assert evaluated == ref.levels[k][1]  # the successors the search generates out of this level
+            assert [counts[n] for n in LAWS] == [0] * 5, k
+            for n in WITNESSES:
+                if counts[n] and n not in first_false:
+                    first_false[n] = (k, counts[n], evaluated)
+    assert first_false == {"TermsFrozen": (1, 2, 4), "LeadersStay": (10, 4, 1124),
+                           "CommitNeverDecreases": (16, 2, 766)}
+
+
+def test_stuttering_steps_satisfy_every_action(model_levels):
+    cfg, vc, levels = model_levels
+
+    def stutters(c, states):
+        succ = [(s, t) for s in states for _, t in rv.next_states(c, s)]
+        return len(succ), sum(1 for s, t in succ if t == s)
+
+    rows, states = levels[1]  # level 2
+    assert (len(rows),) + stutters(vc, states) == (3, 16, 4)
+    with rtla.Actions(cfg, "Stutter == [][FALSE]_vars") as acts:
+        assert rtla.pred_step_replay(acts, rows)[1:] == ({"Stutter": 12}, 16)
+        assert rtla.pred_step_replay(acts, levels[0][0])[1:] == ({"Stutter": 4}, 4)  # Init: no stuttering successor
+    cfg2, vc2, rows2, states2 = make_case(*SHAPES[1])
+    assert stutters(vc2, states2[:SUCC_ROWS]) == (5168, 2)
+    with rtla.Actions(cfg2, "Stutter == [][FALSE]_vars") as acts:
+        assert rtla.pred_step_replay(acts, rows2[:SUCC_ROWS])[1:] == ({"Stutter": 5166}, 5168)
+
+
+# ---- evaluation errors
+
+UNGUARDED = [
+    (r"\A i \in Server : log'[i][1].term >= 1", r"\A i \in Server : Len(log'[i]) >= 1 => log'[i][1].term >= 1"),
+    (r"\A i \in Server : currentTerm'[votedFor'[i]] >= 1",
+     r"\A i \in Server : votedFor'[i] # Nil => currentTerm'[votedFor'[i]] >= 1"),
+]
+
+
+@pytest.mark.parametrize("bad,good", UNGUARDED)
+def test_evaluation_errors_are_errors(bad, good):
+    cfg, _, rows, _ = make_case(*SHAPES[1])
+    with rtla.Actions(cfg, "A == " + _act(bad)) as acts:
+        with pytest.raises(rtla.RtlaError) as e:
+            rtla.pred_step_replay(acts, rows[:SUCC_ROWS])
+        assert e.value.status == rtla.E_SPEC and e.value.flags & rtla.CAP_SPEC_ERROR
+    with rtla.Actions(cfg, "A == " + _act(good)) as acts:
+        masks, counts, evaluated = rtla.pred_step_replay(acts, rows[:SUCC_ROWS])
+        assert counts == {"A": 0} and not any(masks) and evaluated == 5168
+
+
+# ---- compile errors
+
+def nested(depth, body="TRUE", dom=r"DOMAIN messages'"):
+    return "".join(r"\A m%d \in %s : " % (k, dom) for k in range(depth)) + body
+
+
+COMPILE_ERRORS = [
+    # a prime outside [][...]_vars
+    ("A == [][TRUE]_vars\nP == \\A i \\in Server : currentTerm'[i] = 1", "2:35: ''' is not supported"),
+    ("P == \\A i \\in Server : currentTerm'[i] = 1", "1:35: ''' is not supported"),
+    # a prime on a bound variable, a constant, an expression
+    ("A == [][\\A i \\in Server : i' = i]_vars", "1:28: only a state variable may carry a prime"),
+    ("A == [][Leader' = Leader]_vars", "1:15: only a state variable may carry a prime"),
+    ("A == [][(1 + 1)' = 2]_vars", "1:16: only a state variable may carry a prime"),
+    # a message or election belongs to the row its binder ranged over
+    ("A == [][\\A m \\in DOMAIN messages : messages'[m] = 1]_vars",
+     "1:46: type error: a message of the unprimed row indexes the bag of the primed row"),
+    ("A == [][\\A m \\in DOMAIN messages' : messages[m] = 1]_vars",
+     "1:46: type error: a message of the primed row indexes the bag of the unprimed row"),
+    ("A == [][\\A m1 \\in DOMAIN messages : \\A m2 \\in DOMAIN messages' : m1 = m2]_vars",
+     "1:71: type error: a message of the unprimed row compared with one of the primed row"),
+    ("A == [][\\A e \\in elections : \\A f \\in elections' : e # f]_vars",
+     "1:56: type error: a election of the unprimed row compared with one of the primed row"),
+    # the subscript
+    ("A == [][TRUE]", "1:14: expected _vars"),
+    ("A == [][TRUE]_foo", "1:14: expected _vars"),
+    ("A == [][TRUE", "1:13: expected ]_vars"),
+    ("\n".join("A%d == [][TRUE]_vars" % k for k in range(9)), "9:1: more than 8 action definitions"),
+    # a state definition of the same text is still checked
+    ("A == [][TRUE]_vars\nP == 1 + 1", "2:6: type error: a definition must be Boolean"),
+    ("A == [][TRUE]_vars\nA == FALSE", "2:1: 'A' is defined twice"),
+    # no action definition at all
+    ("P == TRUE\nQ == FALSE", "1:1: the text holds no action definition"),
+]
+
+
+@pytest.mark.parametrize("text,message", COMPILE_ERRORS)
+def test_compile_errors_give_line_and_column(text, message):
+    with pytest.raises(rtla.RtlaError) as e:
+        rtla.Actions(rtla.Config(3, 2, 3, 2, 1, 0, ()), text)
+    assert e.value.status == rtla.E_ARG
+    assert "rtla_pred_compile_step: " + message in str(e.value), str(e.value)
+
+
+def test_the_state_compiler_still_refuses_action_definitions():
+    cfg = rtla.Config(3, 2, 3, 2, 1, 0, ())
+    for text in ("A == [][TRUE]_vars", MCACTIONS):
+        with pytest.raises(rtla.RtlaError) as e:
+            rtla.Predicates(cfg, text)
+        assert e.value.status == rtla.E_ARG and "expected an expression" in str(e.value)
+    # a text of both kinds: the step compiler takes the action definitions, in file order, whatever their number
+    # of state definitions
+    both = "\n".join("S%d == TRUE" % k for k in range(9)) + "\nA == [][TRUE]_vars\nT == FALSE\nB == [][FALSE]_vars"
+    with rtla.Actions(cfg, both) as acts:
+        assert acts.names == ["A", "B"]
+
+
+def test_the_step_bound_counts_either_row_at_its_capacity():
+    """Three nested quantifiers over DOMAIN messages' at bag_cap = 64 (tests/test_pred_host.py's bound, on
+    the primed row, whatever the successor's bag holds): a body of 2 steps stays under 2^20, one of 3 steps
+    goes over."""
+    cfg = rtla.Config(2, 1, 3, 1, 1, 0, (), bag_cap=64)
+
+    def steps(b):
+        return 2 + 64 * (3 + 64 * (3 + 64 * (b + 1))) + 2
+
+    assert steps(2) <= 1 << 20 < steps(3)
+    with rtla.Actions(cfg, "A == " + _act(nested(3, "~ TRUE"))) as acts:
+        assert acts.names == ["A"]
+    with pytest.raises(rtla.RtlaError) as e:
+        rtla.Actions(cfg, "A == " + _act(nested(3, "~ ~ TRUE")))
+    assert "1:1: the set's worst case is %d steps per row, above the bound of 1048576" % steps(3) in str(e.value)
+
+
+def test_a_set_knows_its_kind_threads_and_empty_batches():
+    import ctypes as C
+    cfg, _, rows, _ = make_case(*SHAPES[1])
+    rows = rows[:SUCC_ROWS]
+    cc = cfg.c()
+    flat, n = rtla._flat_rows(rows, rtla.row_words(cfg))
+    masks = (C.c_int32 * n)()
+    with rtla.Actions(cfg, MCACTIONS) as acts, rtla.Predicates(cfg, "P == TRUE") as preds:
+        assert rtla._lib.rtla_pred_is_step(acts._h) == 1 and rtla._lib.rtla_pred_is_step(preds._h) == 0
+        assert rtla._lib.rtla_pred_is_step(None) == rtla.E_ARG
+        assert rtla.pred_step_replay(acts, rows, threads=1) == rtla.pred_step_replay(acts, rows, threads=0)
+        assert rtla.pred_step_replay(acts, []) == ([], dict.fromkeys(acts.names, 0), 0)
+        # evaluated may be NULL
+        assert rtla._lib.rtla_pred_step_replay(C.byref(cc), acts._h, flat, n, 0, masks, None, None) == rtla.OK
+        # a state set given to a step call, a step set given to a state call
+        assert rtla._lib.rtla_pred_step_replay(C.byref(cc), preds._h, flat, n, 0, masks, None, None) == rtla.E_ARG
+        assert rtla._lib.rtla_pred_replay(C.byref(cc), acts._h, flat, n, 0, masks, None) == rtla.E_ARG
+        for fn in (rtla.pred_replay,):
+            with pytest.raises(rtla.RtlaError) as e:
+                fn(acts, rows)
+            assert e.value.status == rtla.E_ARG
+        with pytest.raises(rtla.RtlaError) as e:
+            rtla.pred_step_replay(preds, rows)
+        assert e.value.status == rtla.E_ARG
+        # bound to the layout it was compiled for
+        other = rtla.Config(2, 2, 3, 2, 1, 0, (), bag_cap=12)
+        oc = other.c()
+        oflat, on = rtla._flat_rows(rtla.random_rows(other, 0, 4), rtla.row_words(other))
+        assert rtla._lib.rtla_pred_step_replay(C.byref(oc), acts._h, oflat, on, 0, masks, None, None) == rtla.E_ARG
+
+
+# ---- compiler and host replay under a sanitizer: host code, a stand-alone program
+
+def corpus():
+    texts = [MCACTIONS, probe_text(PROBE_SETS[0]), probe_text(PROBE_SETS[1]), "Stutter == [][FALSE]_vars"]
+    texts += [t for t, _ in COMPILE_ERRORS]
+    texts += ["A == " + _act(x) for pair in UNGUARDED for x in pair]
+    return texts
+
+
+def test_compiler_and_replay_under_address_and_undefined_sanitizers(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "step_replay")
+    csrc = os.path.join(ROOT, "raft-tla_amd", "csrc")
+    build = subprocess.run([cxx, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-I", csrc, "-I", os.path.join(ROOT, "include"),
+                            os.path.join(ROOT, "tests", "step_replay_main.cpp"),
+                            os.path.join(csrc, "rtla_pred.cpp"), "-o", exe], capture_output=True, text=True)
+    if build.returncode != 0 and ("asan" in build.stderr or "ubsan" in build.stderr or "sanitize" in build.stderr):
+        pytest.skip("the compiler has no sanitizer runtime")
+    assert build.returncode == 0, build.stderr
+    path = tmp_path / "corpus.txt"
+    path.write_bytes(b"\x1e".join(t.encode() for t in corpus()))
+    run = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "programs" in run.stdout and "ok" in run.stdout
