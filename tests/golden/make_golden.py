@@ -31,6 +31,14 @@ CASES = {
     "n2_v1_t2_l1": (2, 1, 2, 1, 1, 0, (NTL,), False, True),
     "n3_v1_t2_l1_m2": (3, 1, 2, 1, 1, 2, (NTL,), False, True),
     "n3_v2_t2_l1_m2": (3, 2, 2, 1, 1, 2, (ES, LM), False, True),
+    # the row format's limits (rtla_model.h make_layout), each the smallest exhaustible model that reaches it:
+    "n1_v1_t2_l1_c14": (1, 1, 2, 1, 14, 0, (NTL, ES, LM), True, False),    # 4-bit counts: 14, and 15 out of model
+    "n1_v3_t3_l3": (1, 3, 3, 3, 1, 0, (NTL, ES, LM), True, False),         # V = 3, a universe of 820 logs
+    "n2_v1_t2_l4_m1": (2, 1, 2, 4, 1, 1, (NTL, ES, LM), True, False),      # L = 4: the 5-entry own log
+    "n2_v4_t2_l2_m1": (2, 4, 2, 2, 1, 1, (NTL, ES, LM), True, False),      # V = 4: 2-bit values
+    "n2_v1_t2_l1_c3_m3": (2, 1, 2, 1, 3, 3, (NTL, ES, LM), False, False),  # C = 3 with Duplicate / Drop live
+    "n2_v1_t5_l1_m1": (2, 1, 5, 1, 1, 1, (NTL, ES, LM), False, False),     # 3-bit terms
+    "n1_v1_t5_l4": (1, 1, 5, 4, 1, 0, (NTL, ES, LM), False, False),        # L = 4, T = 5: 781 logs, 25 allLogs words
 }
 # SYMMETRY Permutations(Server) (specs/MC.tla): per-level orbit counts.  "py"
 # cases are also run through the value oracle's independent orbit BFS.
@@ -41,6 +49,11 @@ SYM_CASES = {
     "n3_v1_t2_l1_m1_sym": (3, 1, 2, 1, 1, 1, (NTL,), False, False),
     "n3_v1_t3_l1_m1_ntl_sym": (3, 1, 3, 1, 1, 1, (NTL,), False, False),
     "n3_v1_t2_l1_m2_sym": (3, 1, 2, 1, 1, 2, (NTL,), False, True),
+    # the row format's limits under SYMMETRY
+    "n2_v1_t2_l4_m1_sym": (2, 1, 2, 4, 1, 1, (NTL, ES, LM), True, False),
+    "n2_v4_t2_l2_m1_sym": (2, 4, 2, 2, 1, 1, (NTL, ES, LM), True, False),
+    "n2_v1_t2_l1_c3_m3_sym": (2, 1, 2, 1, 3, 3, (NTL, ES, LM), False, False),
+    "n2_v1_t6_l1_m1_sym": (2, 1, 6, 1, 1, 1, (NTL, ES, LM), False, True),  # T = 6: 3.5e6 orbits
 }
 # Models too large for the CPU oracle to exhaust here: a bounded prefix of
 # complete BFS levels, with each level's state-text hash.  The oracle stops

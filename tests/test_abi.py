@@ -44,6 +44,37 @@ def test_row_layout_and_config_errors():
         rtla.row_words(rtla.Config(max_log=5))
 
 
+def test_configuration_limits():
+    """rtla_row_layout / rtla_row_words accept each maximum of the row format (rtla_model.h make_layout)
+    and the two largest log universes under 1024, and refuse one step past each with RTLA_E_CONFIG."""
+    import rtla
+
+    def cfg(n=2, v=1, t=2, l=1, c=1, m=0, **kw):
+        return rtla.Config(n, v, t, l, c, m, (), **kw)
+
+    def universe(v, t, l):
+        return sum((t * v) ** k for k in range(l + 1))
+
+    for ok in (cfg(n=5), cfg(v=4), cfg(t=6), cfg(l=4), cfg(c=14), cfg(bag_cap=64), cfg(elec_cap=32),
+               cfg(n=5, l=4, c=14, t=5, bag_cap=64, elec_cap=32), cfg(m=63, bag_cap=64), cfg(m=3, bag_cap=4)):
+        lay = rtla.row_layout(ok)
+        assert lay["W"] == rtla.row_words(ok) and lay["W"] % 2 == 1
+        assert lay["slot_words"] <= 2 and lay["srv_words"] <= 6 and lay["elec_words"] <= 6
+        assert len(rtla.init_row(ok)) == lay["W"]
+    for v, t, l, logs in ((4, 6, 2, 601), (1, 5, 4, 781)):
+        assert universe(v, t, l) == logs
+        assert rtla.row_layout(cfg(v=v, t=t, l=l))["all_words"] == (logs + 31) // 32
+    assert universe(1, 6, 4) == 1555 > 1024
+    widest = rtla.row_layout(cfg(n=5, v=1, t=5, l=4, c=14, bag_cap=64, elec_cap=32))
+    assert widest["W"] <= 4 + 1 + 5 * 6 + 32 + 32 * 6 + 2 * 64  # rtla_model.h WMAX
+    for bad in (cfg(n=6), cfg(v=5), cfg(t=7), cfg(l=5), cfg(c=15), cfg(bag_cap=65), cfg(elec_cap=33),
+                cfg(v=1, t=6, l=4), cfg(m=3, bag_cap=3), cfg(m=64, bag_cap=64), cfg(n=0), cfg(c=0)):
+        for fn in (rtla.row_words, rtla.row_layout, rtla.init_row):
+            with pytest.raises(rtla.RtlaError) as e:
+                fn(bad)
+            assert e.value.status == rtla.E_CONFIG, bad
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 5])
 def test_init_row_text_matches_value_oracle(n):
     import raft_values as rv

@@ -436,7 +436,10 @@ def test_fpset_probe_bench_inserts_all():
 
 
 # ---- fingerprint-sharded search (the multi-GPU protocol on one device) ----
-SHARDED = ["n2_v2_t3_l2_m1", "n3_v1_t2_l1_m1", "n2_v1_t2_l1_c2_m2", "n1_v2_t3_l2"]
+# (the last two: the row format's limits -- 4-bit message counts, 2-bit values -- through the exchange)
+SHARDED = ["n2_v2_t3_l2_m1", "n3_v1_t2_l1_m1", "n2_v1_t2_l1_c2_m2", "n1_v2_t3_l2", "n1_v1_t2_l1_c14",
+           "n2_v4_t2_l2_m1"]
+LIMIT_MODELS = ["n1_v1_t2_l1_c14", "n2_v4_t2_l2_m1"]
 
 
 @pytest.mark.parametrize("rows_cap,rehome", [("0", "1"), ("40", "1"), ("0", "0")])
@@ -520,6 +523,18 @@ def test_virtual_shards_tiny_outbox_match_golden(monkeypatch, name, shards, sent
     groups in flight still queue past a region's end take the overflow list
     into the next round -- with and without the sent cache.  Golden counts
     and level contents."""
+    virtual_shards_tiny_outbox_match_golden(monkeypatch, name, shards, sent)
+
+
+@pytest.mark.parametrize("shards,sent", [(2, 1), (8, 0)])
+def test_virtual_shards_tiny_outbox_match_golden_at_the_limits(monkeypatch, shards, sent):
+    """The same with 3-bit terms (n2_v1_t5_l1_m1: the smallest limit model whose levels overflow the
+    regions, and whose states spread evenly over 8 owners; its 1.3e6 states make the host digest of the
+    levels most of a case's ~10 s)."""
+    virtual_shards_tiny_outbox_match_golden(monkeypatch, "n2_v1_t5_l1_m1", shards, sent)
+
+
+def virtual_shards_tiny_outbox_match_golden(monkeypatch, name, shards, sent):
     monkeypatch.setenv("RTLA_OUTBOX_CAP", "4096")
     monkeypatch.setenv("RTLA_SENT_CACHE", str(sent))
     g = GOLD[name]
@@ -545,7 +560,7 @@ def test_virtual_shards_tiny_outbox_match_golden(monkeypatch, name, shards, sent
 
 
 @pytest.mark.parametrize("shards", [2, 3, 8])
-@pytest.mark.parametrize("name", ["n2_v2_t3_l2_m1", "n3_v1_t2_l1_m1", "n2_v1_t2_l1_m1_sym"])
+@pytest.mark.parametrize("name", ["n2_v2_t3_l2_m1", "n3_v1_t2_l1_m1", "n2_v1_t2_l1_m1_sym", "n2_v4_t2_l2_m1"])
 def test_virtual_shards_over_rccl_match_golden(monkeypatch, name, shards):
     """The virtual-shard exchange through a one-rank RCCL communicator
     (RTLA_TRANSPORT=rccl): every fingerprint / answer / row transfer is an
@@ -629,7 +644,18 @@ def test_stored_fingerprints_equal_full_rehash(shards):
     """Every row the search stores carries the fingerprint derived
     incrementally from its parent; it must equal a from-scratch hash of the
     row (a wrong stored fingerprint silently breaks dedup at the next level)."""
-    g = GOLD["n2_v2_t3_l2_m1"]
+    stored_fingerprints_equal_full_rehash("n2_v2_t3_l2_m1", shards)
+
+
+@pytest.mark.parametrize("shards", [1, 2])
+@pytest.mark.parametrize("name", LIMIT_MODELS)
+def test_stored_fingerprints_equal_full_rehash_at_the_limits(name, shards):
+    """The same with message counts up to 14 (and 15 out of the model) and with 2-bit values."""
+    stored_fingerprints_equal_full_rehash(name, shards)
+
+
+def stored_fingerprints_equal_full_rehash(name, shards):
+    g = GOLD[name]
     kw = small_kw(g)
     kw["mem_budget"] *= shards
     cfg = cfg_of(g, shards=shards, chunk=512, **kw)
@@ -648,7 +674,18 @@ def test_stored_fingerprints_equal_full_rehash(shards):
 # ---- checkpoint / recover (TLC -checkpoint / -recover, reference .gitignore:2) ----
 @pytest.mark.parametrize("shards", [1, 2])
 def test_checkpoint_recover_continues_identically(tmp_path, shards):
-    g = GOLD["n2_v2_t3_l2_m1"]
+    checkpoint_recover_continues_identically(tmp_path, "n2_v2_t3_l2_m1", shards)
+
+
+@pytest.mark.parametrize("shards", [1, 2])
+@pytest.mark.parametrize("name", LIMIT_MODELS)
+def test_checkpoint_recover_continues_identically_at_the_limits(tmp_path, name, shards):
+    """The row format's limits through the checkpoint files."""
+    checkpoint_recover_continues_identically(tmp_path, name, shards)
+
+
+def checkpoint_recover_continues_identically(tmp_path, name, shards):
+    g = GOLD[name]
     kw = small_kw(g)
     kw["mem_budget"] *= shards
     cfg = cfg_of(g, shards=shards, chunk=512, **kw)
@@ -769,7 +806,7 @@ def test_symmetry_stored_rows_are_generated_states():
             assert len({rtla.state_text(cfg, r) for r in rows}) == len(rows)
 
 
-@pytest.mark.parametrize("name", ["n2_v2_t3_l2_m1", "n3_v1_t2_l1_m1_sym"])
+@pytest.mark.parametrize("name", ["n2_v2_t3_l2_m1", "n3_v1_t2_l1_m1_sym", "n1_v1_t2_l1_c14", "n2_v4_t2_l2_m1_sym"])
 def test_wave_kernel_matches_golden(name):
     """The wave-per-state k_expand (the fallback for rows too wide for the
     compacting kernel), forced with RTLA_XFLAGS=2048 in a child process (the
@@ -870,7 +907,17 @@ def test_ring_arena_wraps_and_matches_golden(shards):
     """A frontier arena barely larger than the biggest (current + next) level
     pair: every level wraps around the arena at a different offset; counts and
     level contents must still be the oracle's."""
-    g = GOLD["n2_v2_t3_l2_m1"]
+    ring_arena_wraps_and_matches_golden("n2_v2_t3_l2_m1", shards)
+
+
+@pytest.mark.parametrize("shards", [1, 2])
+def test_ring_arena_wraps_and_matches_golden_at_the_limits(shards):
+    """The same with 2-bit values (n2_v4_t2_l2_m1)."""
+    ring_arena_wraps_and_matches_golden("n2_v4_t2_l2_m1", shards)
+
+
+def ring_arena_wraps_and_matches_golden(name, shards):
+    g = GOLD[name]
     x = [n for n, _ in g["levels"]]
     # multi-shard: each shard holds about 1/shards of a level (plus skew)
     need = max(_round64(x[i]) + x[i + 1] for i in range(len(x) - 1))
@@ -932,7 +979,8 @@ def _oracle_coverage(g):
     return r["coverage"]
 
 
-@pytest.mark.parametrize("name", ["n2_v2_t3_l2_m1", "n2_v1_t2_l1_c2_m2", "n3_v1_t2_l1_m1"])
+@pytest.mark.parametrize("name", ["n2_v2_t3_l2_m1", "n2_v1_t2_l1_c2_m2", "n3_v1_t2_l1_m1", "n2_v1_t2_l1_c3_m3",
+                                  "n1_v1_t2_l1_c14"])
 def test_coverage_per_action_matches_oracle(name):
     """-coverage 1 (.vscode/settings.json:5): states generated per action of
     Next, Receive split by handler, equal the oracle's per-action counts."""

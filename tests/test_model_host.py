@@ -10,6 +10,7 @@ import random
 import pytest
 
 import hostmodel
+import limits
 import raft_cpu
 import raft_values as rv
 import rtla
@@ -54,6 +55,93 @@ def test_host_model_synthetic_states_match_value_oracle():
         s = tla_text.parse_state(vc, rtla.state_text(cfg, r))
         ref = sorted((rv.in_model(vc, t), rv.state_text(vc, t)) for _, t in rv.next_states(vc, s))
         assert sorted(by[k]) == ref, "input state %d" % k
+
+
+# ---- the row format's limits (tests/limits.py): widest fields, full capacities, the 256-instance boundary
+
+@pytest.mark.parametrize("name", limits.ALL)
+def test_limit_shapes_expand_as_the_value_oracle(name):
+    """hostmodel.expand over a limit shape's sample equals raft_values.next_states state by state (texts and
+    in-model flags), every stored fingerprint equals a from-scratch hash, and the sample shows every witness
+    of tests/limits.py -- counted on the value oracle's states, printed here."""
+    c = limits.case(name)
+    limits.assert_witnessed(c, "host model")
+    assert limits.kernel_of(c.cfg)[0] == c.kernel  # the table's kernel column, by the launch rule
+    by = collections.defaultdict(list)
+    for k, _, _, im, r in limits.host_expand(name):
+        by[k].append((im, rtla.state_text(c.cfg, r)))
+        assert rtla.stored_fingerprint(r) == rtla.row_fingerprint(c.cfg, r)
+    for k in range(len(c.rows)):
+        assert sorted(by[k]) == list(c.ref[k]), "input state %d" % k
+    assert sum(len(v) for v in by.values()) == c.n_succ > 20 * len(c.rows)
+
+
+@pytest.mark.parametrize("name", limits.ALL)
+def test_limit_shapes_text_round_trip(name):
+    """rtla.state_text -> tla_text.parse_state -> raft_values.state_text is the identity: values up to v4,
+    terms up to 7, counts up to 15, logs of 5 entries.  On every input row, and on successor rows that print
+    each extreme plus an even spread in and out of the model (the parser takes ~5 ms a state; the text of
+    EVERY successor row is compared with the value oracle's print of its own successor by
+    test_limit_shapes_expand_as_the_value_oracle, and here the parse must give that very state)."""
+    c = limits.case(name)
+    limits.assert_witnessed(c, "text round trip")
+    n, v, t, l, cc, _ = c.shape
+    succ = [(k, r, rtla.state_text(c.cfg, r), im) for k, _, _, im, r in limits.host_expand(name)]
+    extremes = {
+        "log entry (T, V)": lambda ln: ln.startswith("/\\ log = ") and "[term |-> %d, value |-> v%d]" % (t, v) in ln,
+        "count C+1": lambda ln: ln.startswith("/\\ messages = ") and "] :> %d" % (cc + 1) in ln,
+        "currentTerm T+1": lambda ln: ln.startswith("/\\ currentTerm = ") and ":> %d" % (t + 1) in ln,
+        "own log of L+1": lambda ln: ln.startswith("/\\ log = ") and any(
+            x.count("[term") == l + 1 for x in ln.split("<<")),
+    }
+    picked = {}
+    for what, fn in extremes.items():
+        hits = [x for x in succ if any(fn(ln) for ln in x[2].split("\n"))]
+        assert hits, what
+        picked[what] = len(hits)
+        for x in hits[:10]:
+            picked.setdefault("rows", []).append(x)
+    sample = picked.pop("rows") + limits.spread([x for x in succ if not x[3]], 100) + \
+        limits.spread([x for x in succ if x[3]], 150)
+    print("%s: successor texts printing each extreme: %s; %d successors parsed back" % (name, picked, len(sample)))
+    for r, s in zip(c.rows, c.states):
+        assert rv.state_text(c.vc, s) == rtla.state_text(c.cfg, r)
+    for k, r, text, _ in sample:
+        s = tla_text.parse_state(c.vc, text)
+        assert s == c.by_text[k][text] and rv.state_text(c.vc, s) == text
+
+
+def assert_full_bag_successors(c, rows_states, expand):
+    """expand(rows) -- hostmodel.expand or rtla.expand_batch -- over full-bag states (limits.full_bag_rows):
+    per state the value oracle's successors (texts, in-model flags), among them DuplicateMessage and
+    DropMessage of every slot, that of slot K - 1 under the layout's highest instance id."""
+    cfg, vc = c.cfg, c.vc
+    ninst = limits.n_instances(cfg)
+    assert rows_states, "no full-bag state in the sample"
+    got = collections.defaultdict(list)
+    for k, inst, sub, im, r in expand([list(r) for r, _ in rows_states]):
+        got[k].append((inst, sub, im, rtla.state_text(cfg, r)))
+    for k, (_, s) in enumerate(rows_states):
+        ref = rv.next_states(vc, s)
+        assert sorted((im, t) for _, _, im, t in got[k]) == sorted((rv.in_model(vc, u), rv.state_text(vc, u))
+                                                                   for _, u in ref), "full-bag state %d" % k
+        for label, first in (("DuplicateMessage", ninst - 2 * c.K), ("DropMessage", ninst - c.K)):
+            mine = [(inst, t) for inst, sub, _, t in got[k] if rtla.action_name(cfg, inst, sub) == label]
+            assert [inst for inst, _ in mine] == list(range(first, first + c.K)), label
+            assert sorted(t for _, t in mine) == sorted(rv.state_text(vc, u) for lab, u in ref if lab == label)
+        assert got[k][-1][0] == ninst - 1  # (sorted by instance: the last successor is DropMessage of slot K - 1)
+    return ninst - 1
+
+
+@pytest.mark.parametrize("name", limits.BOUNDARY)
+def test_full_bag_drop_of_the_last_slot_is_the_highest_instance(name):
+    """At the 256-instance boundary (255, 256, 258 and 264 instances): the host model on states whose bag
+    holds K messages."""
+    c = limits.case(name)
+    last = assert_full_bag_successors(c, limits.full_bag_rows(name),
+                                      lambda rows: hostmodel.expand(c.cfg, rows, len(rows[0])))
+    print("%s: %d full-bag states, highest instance id %d" % (name, len(limits.full_bag_rows(name)), last))
+    assert last == {"n4_v4_k64": 255, "n5_k60": 254, "n5_k61": 257, "n5_k63": 263}[name]
 
 
 # ---- the three 64-bit records (rtla_device.h), through tests/hostmodel.cpp

@@ -11,9 +11,10 @@ import subprocess
 
 import pytest
 
+import limits
 import raft_values as rv
 import rtla
-from test_safety_host import ALL, SHAPES
+from test_safety_host import ALL, SHAPES, py_mask
 from test_safety_host import setup as make_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,6 +130,38 @@ def test_field_predicates_take_both_values():
     for name, _, _ in FIELD_PREDICATES:
         fr = FRACTION[name]
         assert len(fr) == len(SHAPES) and any(0.05 <= f <= 0.95 for f in fr), (name, fr)
+
+
+# ---- the row format's limits (tests/limits.py): the interpreter reads every field by the layout
+
+@pytest.mark.parametrize("name", limits.TWO)
+def test_limit_shapes_predicates_match_the_python_functions(name):
+    """At 3-bit terms with 2-bit values, and at L = 4 with all 64 bag slots and 32 election records: the
+    restated built-ins against the Python predicates of test_safety_host.py, the field predicates against
+    their Python functions, over the sample's rows and a spread of the host model's successor rows in and
+    out of the model (terms of T + 1, logs of L + 1 entries, counts of C + 1, full bags)."""
+    c = limits.case(name)
+    limits.assert_witnessed(c, "pred_replay")
+    succ = limits.host_expand(name)
+    succ = limits.spread([x for x in succ if not x[3]], 150) + limits.spread([x for x in succ if x[3]], 250)
+    rows = list(c.rows) + [r for _, _, _, _, r in succ]
+    states = list(c.states) + [c.state_of(k, r) for k, _, _, _, r in succ]
+    with rtla.Predicates(c.cfg, MCPRED) as preds:
+        masks, counts = rtla.pred_replay(preds, rows)
+        bit = {k: rtla.INV_BITS[RESTATED[n]] for k, n in enumerate(preds.names[:5])}
+    want = [py_mask(c.vc, s) for s in states]
+    assert [sum(b for k, b in bit.items() if m >> k & 1) for m in masks] == want
+    assert {RESTATED[n]: counts[n] for n in RESTATED} == {n: sum(1 for w in want if w & b)
+                                                          for n, b in rtla.INV_BITS.items()}
+    assert all(counts[n] for n in RESTATED), counts
+    for group in FIELD_SETS:
+        text = "\n".join("%s == %s" % (nm, src) for nm, src, _ in group)
+        with rtla.Predicates(c.cfg, text) as preds:
+            masks, counts = rtla.pred_replay(preds, rows)
+        for k, (nm, _, fn) in enumerate(group):
+            want = [fn(c.vc, s) for s in states]
+            assert [not (m >> k & 1) for m in masks] == want, nm
+            assert counts[nm] == want.count(False)
 
 
 # ---- evaluation errors

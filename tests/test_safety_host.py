@@ -6,6 +6,7 @@ succ=0) and on successors evaluated as parent + delta (check_replay succ=1
 against the predicates over raft_values.next_states)."""
 import pytest
 
+import limits
 import raft_values as rv
 import rtla
 import tla_text
@@ -106,6 +107,34 @@ def test_threads_agree(case):
         sub = rows[:600]
         assert rtla.check_replay(cfg, sub, ALL, succ=succ, threads=1) == rtla.check_replay(cfg, sub, ALL, succ=succ,
                                                                                            threads=0)
+
+
+# ---- the row format's limits (tests/limits.py)
+
+@pytest.mark.parametrize("name", limits.ALL)
+def test_limit_shapes_check_replay(name):
+    """check_replay at the widest fields and full capacities, succ 0 and 1, against the Python predicates
+    over the value oracle's states and reference successors; every invariant is violated on some row."""
+    c = limits.case(name)
+    limits.assert_witnessed(c, "check_replay")
+    want = [py_mask(c.vc, s) for s in c.states]
+    masks, counts = rtla.check_replay(c.cfg, c.rows, ALL)
+    assert masks == want
+    assert counts == {n: sum(1 for w in want if w & b) for n, b in rtla.INV_BITS.items()}
+    assert all(counts.values()), counts
+    want, per_bit = [], dict.fromkeys(ALL, 0)
+    for nxt in c.succ:
+        acc = 0
+        for _, t in nxt:
+            m = py_mask(c.vc, t)
+            acc |= m
+            for n, b in rtla.INV_BITS.items():
+                per_bit[n] += 1 if m & b else 0
+        want.append(acc)
+    masks, counts = rtla.check_replay(c.cfg, c.rows, ALL, succ=True)
+    assert masks == want and counts == per_bit
+    assert all(per_bit.values()), per_bit
+    print("%s: violating rows %s, violating successors %s" % (name, dict(counts), per_bit))
 
 
 # ---- hand cases: rows built by editing packed fields of the Init row (rtla_model.h make_layout / srv_pack)

@@ -6,6 +6,7 @@ oracle (raft_values), so the walk semantics are pinned without a GPU."""
 import pytest
 
 import hostmodel
+import limits
 import raft_values as rv
 import rtla
 import tla_text
@@ -81,6 +82,35 @@ def test_walks_match_independent_rederivation(shape):
             prev = cur
         # the end record is the walk's: length, last fingerprint, stop code, path digest
         assert ends[w] == rtla.stored_fingerprint(steps[-1][2]) + (digest_of([r for _, _, r in steps]), 30, 0)
+
+
+def test_walks_from_limit_shape_rows_match_independent_rederivation():
+    """The same re-derivation at the row format's limits (tests/limits.py: 3-bit terms, 2-bit values,
+    counts up to 14), walk w started from a row of the sample instead of Init: the rows whose bag and
+    election list have room for one more entry per step (a walk that fills either is a capacity error)."""
+    c = limits.case("n3_v4_t6_c14")
+    limits.assert_witnessed(c, "walks")
+    cfg, words, depth = c.cfg, len(c.rows[0]), 8
+    room = [k for k, s in enumerate(c.states) if len(s[rv.IX["messages"]]) + depth < c.K
+            and len(s[rv.IX["elections"]]) + depth < c.E]
+    rows, walks = [list(c.rows[k]) for k in room], len(room)
+    assert walks >= 12
+    ends = rtla.sim_replay(cfg, rows, walks, depth, seed=SEED).ends
+    lengths = []
+    for w in range(walks):
+        violating, steps = rtla.sim_walk(cfg, rows[w], w, depth, seed=SEED)
+        mine = python_walk(cfg, words, rows[w], w, depth, SEED)
+        assert not violating and [(i, r) for i, _, r in steps] == mine
+        prev = c.states[room[w]]
+        for _, _, row in steps:
+            cur = tla_text.parse_state(c.vc, rtla.state_text(cfg, row))
+            assert rv.in_model(c.vc, cur) and cur in [s for _, s in rv.next_states(c.vc, prev)]
+            prev = cur
+        stop = rtla.SIM_STOP_DEPTH if len(steps) == depth else rtla.SIM_STOP_STUCK
+        last = steps[-1][2] if steps else rows[w]
+        assert ends[w] == rtla.stored_fingerprint(last) + (digest_of([r for _, _, r in steps]), len(steps), stop)
+        lengths.append(len(steps))
+    assert sum(lengths) > walks * depth // 2, lengths
 
 
 def test_path_digest_sees_one_changed_intermediate_pick():

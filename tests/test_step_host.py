@@ -13,6 +13,7 @@ import subprocess
 import pytest
 
 import hostmodel
+import limits
 import raft_values as rv
 import rtla
 import tla_text
@@ -113,12 +114,13 @@ def probe_text(group):
     return "\n".join("%s == %s" % (name, _act(src)) for name, src, _ in group)
 
 
-def python_side(vc, states, named):
-    """(masks, counts, evaluated) of the definitions `named` [(name, fn)] over every step out of `states`."""
+def python_side(vc, states, named, succ=None):
+    """(masks, counts, evaluated) of the definitions `named` [(name, fn)] over every step out of `states`
+    (succ: their raft_values.next_states, where the caller already has them)."""
     masks, counts, evaluated = [], dict.fromkeys([n for n, _ in named], 0), 0
-    for s in states:
+    for k, s in enumerate(states):
         acc = 0
-        for _, t in rv.next_states(vc, s):
+        for _, t in (succ[k] if succ is not None else rv.next_states(vc, s)):
             evaluated += 1
             if t == s:
                 continue
@@ -166,6 +168,27 @@ def test_the_laws_hold_on_random_rows(case):
     want = python_side(vc, states, [(n, MC_PY[n]) for n in acts.names])
     assert (masks, counts, evaluated) == want
     assert [counts[n] for n in LAWS] == [0] * 5 and all(counts[n] > 0 for n in WITNESSES)
+
+
+# ---- the row format's limits (tests/limits.py): both rows of a step read by the layout
+
+@pytest.mark.parametrize("name", limits.TWO)
+def test_limit_shapes_steps_match_the_python_functions(name):
+    """specs/MCActions.tla and the field probes on every step out of a limit shape's sample -- successors
+    with a term of T + 1, a log of L + 1 entries, a count of C + 1, a bag of K messages -- against the
+    Python functions over the value oracle's (state, successor) pairs."""
+    c = limits.case(name)
+    limits.assert_witnessed(c, "pred_step_replay")
+    with rtla.Actions(c.cfg, MCACTIONS) as acts:
+        named = [(n, MC_PY[n]) for n in acts.names]
+        got = rtla.pred_step_replay(acts, c.rows)
+    want = python_side(c.vc, c.states, named, c.succ)
+    assert got == want and want[2] == c.n_succ
+    assert [want[1][n] for n in LAWS] == [0] * 5 and all(want[1][n] > 0 for n in WITNESSES)
+    for group in PROBE_SETS:
+        named = [(nm, fn) for nm, _, fn in group]
+        with rtla.Actions(c.cfg, probe_text(group)) as acts:
+            assert rtla.pred_step_replay(acts, c.rows) == python_side(c.vc, c.states, named, c.succ)
 
 
 # ---- the whole model n2_v1_t2_l1_m1, level by level

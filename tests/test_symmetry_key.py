@@ -14,8 +14,8 @@ import random
 
 import pytest
 
+import limits
 import rtla
-
 
 
 def cfg_of(n):
@@ -71,6 +71,41 @@ def test_orbit_key_is_a_function_of_the_orbit(n):
     # ordering, a pair keeps both; random states: mostly one
     assert nperm[len(base) + 12] == (1 if n >= 3 else len(all_perms))
     assert sum(nperm[:len(base)]) <= 1.5 * len(base), nperm[:len(base)]
+
+
+@pytest.mark.parametrize("name", limits.SYMMETRIC)
+def test_limit_shapes_orbit_key_and_orbit_text(name):
+    """At the row format's limits (tests/limits.py; N = 5 with L = 4 and counts up to 15, N = 4 with
+    |Value| = 4): over sample rows, successor rows in and out of the model and permuted copies, orbit_key
+    is constant over all N! images, two rows share a key exactly when they share the value oracle's orbit
+    text, and rtla.orbit_text equals it."""
+    import raft_values as rv
+    import tla_text
+    c = limits.case(name)
+    limits.assert_witnessed(c, "orbit key")
+    cfg, n = c.with_cfg(symmetry=True), c.shape[0]
+    all_perms = [list(p) for p in itertools.permutations(range(n))]
+    rng = random.Random(200 + n)
+    succ = limits.host_expand(name)
+    out = [list(r) for _, _, _, im, r in succ if not im]
+    inm = [list(r) for _, _, _, im, r in succ if im]
+    rows = [list(r) for r in c.rows[:8]] + out[::max(1, len(out) // 6)][:6] + inm[::max(1, len(inm) // 6)][:6]
+    rows += [rtla.permute_row(cfg, r, rng.choice(all_perms[1:])) for r in rows[::2]]
+    keys, texts = [], []
+    for r in rows:
+        key = rtla.orbit_key(cfg, r)[0]
+        for pi in all_perms:
+            assert rtla.orbit_key(cfg, rtla.permute_row(cfg, r, pi))[0] == key
+        t = rtla.orbit_text(cfg, r)
+        assert t == rv.orbit_text(c.vc, tla_text.parse_state(c.vc, rtla.state_text(cfg, r)))
+        keys.append(key)
+        texts.append(t)
+    by_key = {}
+    for k, t in zip(keys, texts):
+        by_key.setdefault(k, set()).add(t)
+    assert all(len(v) == 1 for v in by_key.values())
+    assert len(by_key) == len(set(texts)) == 20  # (the copies add no orbit)
+    assert rtla.rows_orbit_hash(cfg, rows, threads=2) == sum(rv.fnv1a64(t) for t in texts) & (2 ** 64 - 1)
 
 
 def test_permute_row_keeps_state_validity():
