@@ -1,11 +1,9 @@
-// rtla_audit.cpp -- invariants evaluated outside the search (semantics:
-// rtla_audit.h).  rtla_check_batch and rtla_check_frontier run the audit
-// kernels (rtla_kaudit.hip), over host rows staged into a device buffer or
-// over the frontier where it lies; rtla_check_replay computes the same on the
-// host (audit_row_serial), with no GPU.
-#include <atomic>
-#include <thread>
-
+// rtla_audit.cpp -- passes over rows outside the search (semantics:
+// rtla_audit.h): audit_batch runs a pass's kernel over host rows staged into a
+// device buffer, audit_frontier over the frontier where it lies.  The
+// invariant audit is here too: rtla_check_batch and rtla_check_frontier are
+// those two with the audit kernels (rtla_kaudit.hip); rtla_check_replay
+// computes the same on the host (audit_row_serial), with no GPU.
 #include "rtla_audit.h"
 #include "rtla_ctx.h"
 
@@ -30,32 +28,11 @@ extern "C" int rtla_check_replay(const rtla_cfg* c, const uint32_t* rows, size_t
   CFG_LAYOUT(L, c);
   if (!audit_args_ok(inv_mask, succ) || threads < 0 || !masks || (n && !rows)) return RTLA_E_ARG;
   L.inv_mask = inv_mask;
-  const int nt = (int)std::min<size_t>((size_t)std::min(text_threads(threads), 16), std::max<size_t>(1, n / 256));
-  std::vector<AuditCounters> part((size_t)nt, audit_zero());
-  std::atomic<size_t> next{0};
-  auto work = [&](int t) {
-    AuditCounters& tl = part[(size_t)t];
-    for (;;) {
-      const size_t b = next.fetch_add(256);
-      if (b >= n) break;
-      for (size_t k = b; k < std::min(n, b + 256); k++)
-        masks[k] = dispatch_n(L, [&](auto ns) {
-          return audit_row_serial<decltype(ns)::value>(L, rows + k * (size_t)L.W, k, succ, tl);
-        });
-    }
-  };
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
-  work(0);
-  for (auto& th : pool) th.join();
-  AuditCounters sum = audit_zero();
-  for (const AuditCounters& p : part) {
-    sum.flags |= p.flags;
-    for (int k = 0; k < AUDIT_COUNTS; k++) sum.counts[k] += p.counts[k];
-  }
-  if (sum.flags) return flags_to_status(sum.flags);
-  audit_counts_out(sum, counts);
-  return RTLA_OK;
+  return replay_rows(n, threads, masks, counts, nullptr, [&](size_t k, AuditCounters& tl) {
+    return dispatch_n(L, [&](auto ns) {
+      return audit_row_serial<decltype(ns)::value>(L, rows + k * (size_t)L.W, k, succ, tl);
+    });
+  });
 }
 
 // Stateless, like rtla_expand_batch: the rows are staged into a device buffer
@@ -101,11 +78,8 @@ extern "C" int rtla_check_batch(const rtla_cfg* c, const uint32_t* rows, size_t 
   }, masks, counts);
 }
 
-int audit_frontier(rtla_ctx* x, int succ, int kind, const AuditLaunch& launch, rtla_audit_stats* out) {
-  const bool step = kind == AUDIT_PRED_STEP;
-  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
-      x->sh[0].n_cur == 0)
-    return RTLA_E_STATE;
+int audit_frontier(rtla_ctx* x, int succ, const AuditLaunch& launch, rtla_audit_stats* out) {
+  if (!frontier_pass_ok(x)) return RTLA_E_STATE;
   HIPCHK(hipSetDevice(x->device));
   Shard& s = x->sh[0];
   AuditState& a = x->audit;
@@ -130,10 +104,10 @@ int audit_frontier(rtla_ctx* x, int succ, int kind, const AuditLaunch& launch, r
   } else if (h.viol_key != AUDIT_NO_VIOLATION) {
     status = RTLA_VIOLATION;
     a.viol = true;
-    a.start = s.cur_base + (step ? step_key_index(h.viol_key) : audit_key_index(h.viol_key));
-    a.inst = !succ ? -1 : step ? step_key_inst(h.viol_key) : audit_key_inst(h.viol_key);
-    a.mask = kind != AUDIT_INVARIANTS ? pred_key_mask(h.viol_key) : audit_key_mask(h.viol_key);
-    a.in_model = step ? step_key_in_model(h.viol_key) : kind == AUDIT_PRED_STATE ? 1 : audit_key_in_model(h.viol_key);
+    a.start = s.cur_base + audit_key_index(h.viol_key);
+    a.inst = succ ? audit_key_inst(h.viol_key) : -1;
+    a.mask = audit_key_mask(h.viol_key);
+    a.in_model = audit_key_in_model(h.viol_key);
   }
   if (out) {
     memset(out, 0, sizeof *out);
@@ -159,13 +133,11 @@ int audit_frontier(rtla_ctx* x, int succ, int kind, const AuditLaunch& launch, r
 
 extern "C" int rtla_check_frontier(rtla_ctx* x, int32_t inv_mask, int32_t succ, rtla_audit_stats* out) {
   if (!x) return RTLA_E_ARG;
-  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
-      x->sh[0].n_cur == 0)
-    return RTLA_E_STATE;
+  if (!frontier_pass_ok(x)) return RTLA_E_STATE;
   if (!audit_args_ok(inv_mask, succ)) return RTLA_E_ARG;
   Layout L = x->L;
   L.inv_mask = inv_mask;
-  return audit_frontier(x, succ, AUDIT_INVARIANTS, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
+  return audit_frontier(x, succ, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
     return launch_audit(L, cur, n, succ, m, ctr, st);
   }, out);
 }

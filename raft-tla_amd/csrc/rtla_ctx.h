@@ -3,17 +3,19 @@
 //   rtla_comm.cpp     collectives and transfers between shards (RCCL, shared memory, device copies)
 //   rtla_ckpt.cpp     checkpoint / recover
 //   rtla_simhost.cpp  random-walk simulation
-//   rtla_audit.cpp    invariants outside the search: batch, host replay, frontier audit
-//   rtla_predhost.cpp user-defined predicates: the rtla_pred_* ABI over the compiler (rtla_pred.cpp) and the audit
+//   rtla_audit.cpp    passes over rows outside the search (batch, host replay, frontier), and the invariant audit
+//   rtla_predhost.cpp user-defined predicates: the rtla_pred_* ABI over the compiler (rtla_pred.cpp) and those passes
 //   rtla_rows.cpp     the context-free row API, synthetic and probe micro-benchmarks
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <functional>
+#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -138,6 +140,13 @@ struct rtla_ctx {
   }
 };
 
+// What a pass over the frontier where it lies (audits, predicates, steps, random walks) needs, else RTLA_E_STATE:
+// a search of one shard in one process that keeps rows, initialised, with no violation of its own and rows to read.
+inline bool frontier_pass_ok(rtla_ctx* x) {
+  return x->cfg.mode != RTLA_MODE_DEDUP && x->world == 1 && x->nshard == 1 && x->inited && !x->viol_shard() &&
+         x->sh[0].n_cur != 0;
+}
+
 // A failing HIP call is reported and ends the function with `ret`.
 #define HIPCHK_RET(x, ret)                                                                          \
   do {                                                                                              \
@@ -194,17 +203,61 @@ int env_xflags();
 int layout_from_cfg(const rtla_cfg* c, Layout* L);
 bool fault_here(const rtla_ctx* x, const char* where);
 void print_stamps(const DevCounters& c, int level);
-// rtla_audit.cpp: one audit launch (`launch`: the kernel, over the ring, row count, device counters and stream it
-// is given) over host rows staged into a device buffer / over the context's frontier where it lies.  kind
-// (AuditKind): whether the masks are RTLA_INV_* bits (audit_key), a predicate set's definition bits on rows
-// (pred_key) or an action set's on steps (step_key).  evaluated (may be null): the evaluated states / steps.
+// rtla_audit.cpp: one pass (`launch`: the kernel, over the ring, row count, device counters and stream it is
+// given) over host rows staged into a device buffer / over the context's frontier where it lies.  The masks'
+// bits are what the kernel evaluates (RTLA_INV_* bits, a predicate or action set's definitions); the key is
+// audit_key.  succ: the pass evaluates successors (a violation has an instance).  evaluated (may be null): the
+// evaluated states / steps.
 using AuditLaunch = std::function<hipError_t(const Ring&, uint64_t, int*, AuditCounters*, hipStream_t)>;
 AuditCounters audit_zero();
 int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaunch& launch, int32_t* masks,
                 uint64_t* counts, uint64_t* evaluated = nullptr);
-int audit_frontier(rtla_ctx* x, int succ, int kind, const AuditLaunch& launch, rtla_audit_stats* out);
+int audit_frontier(rtla_ctx* x, int succ, const AuditLaunch& launch, rtla_audit_stats* out);
 // rtla_rows.cpp
 int text_threads(int want);
+
+// work(t, begin, end) for every chunk of `chunk` items of [0, n), handed out in ascending order to `threads`
+// threads as each comes free (t: the thread, 0 the caller's own); returns when all are done.
+template <class F>
+void parallel_chunks(size_t n, size_t chunk, int threads, F work) {
+  std::atomic<size_t> next{0};
+  auto run = [&](int t) {
+    for (;;) {
+      const size_t b = next.fetch_add(chunk);
+      if (b >= n) break;
+      work(t, b, std::min(n, b + chunk));
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < threads; t++) pool.emplace_back(run, t);
+  run(0);
+  for (auto& th : pool) th.join();
+}
+
+// The host replay of a pass over n rows: masks[k] = row(k, tally), the tally being that of the thread that took
+// the row's 256-row chunk; the threads' flags, counts and evaluated states are merged.
+template <class F>
+int replay_rows(size_t n, int threads, int32_t* masks, uint64_t* counts, uint64_t* evaluated, F row) {
+  const int nt = (int)std::min<size_t>((size_t)std::min(text_threads(threads), 16), std::max<size_t>(1, n / 256));
+  std::vector<AuditCounters> part((size_t)nt, audit_zero());
+  auto merge = [](AuditCounters& into, const AuditCounters& p) {
+    into.flags |= p.flags;
+    into.evaluated += p.evaluated;
+    for (int k = 0; k < AUDIT_COUNTS; k++) into.counts[k] += p.counts[k];
+  };
+  parallel_chunks(n, 256, nt, [&](int t, size_t b, size_t e) {
+    AuditCounters tl = audit_zero();  // the chunk's own: the threads' tallies lie side by side in memory
+    for (size_t k = b; k < e; k++) masks[k] = row(k, tl);
+    merge(part[(size_t)t], tl);
+  });
+  AuditCounters sum = audit_zero();
+  for (const AuditCounters& p : part) merge(sum, p);
+  if (sum.flags) return flags_to_status(sum.flags);
+  if (counts)
+    for (int k = 0; k < AUDIT_COUNTS; k++) counts[k] = sum.counts[k];
+  if (evaluated) *evaluated = sum.evaluated;
+  return RTLA_OK;
+}
 uint64_t rows_digest(const Layout& L, const uint32_t* rows, size_t n, int threads, bool orbit = false);
 int expand_batch_dev(const Layout& L, const uint32_t* d_rows, size_t n, std::vector<uint32_t>& out,
                      std::vector<uint64_t>& info, hipStream_t st);

@@ -1,23 +1,22 @@
 // rtla_kaudit.hip -- the audit kernels: invariants evaluated outside the
 // search, over a batch of rows or over the frontier in HBM (semantics in
 // rtla_audit.h; the host replay computes the same masks, counts and key).
-//   * k_audit_state: the rows themselves.  A pure stream over the rows: a wave
-//     takes 64 consecutive rows (a group never wraps the ring), copies them
-//     into LDS with 16-byte loads, coalesced, and each lane then evaluates its
-//     own row there -- the row stride W is odd, so the 64 lanes' reads of word
-//     k fall on different banks.  Rows too wide for 64 to fit are staged in
-//     tiles of `tr` rows.
-//   * k_audit_succ: every enabled successor.  k_expand's shape (rtla_kwave.hip)
-//     with the set, the row building and the outbox removed: one wave per
-//     state, the row in LDS, each lane evaluates one action instance as a
-//     Delta and checks parent + delta.
+//   * k_audit_state: the rows themselves, by audit_row_stream (rtla_kaudit.h):
+//     64 rows per wave staged into LDS in tiles of `tr` rows, each lane
+//     evaluates its own row there.
+//   * k_audit_succ: every enabled successor: one wave per state, the row in
+//     LDS, each lane evaluates one action instance as a Delta and checks
+//     parent + delta.  No set, no row building, no outbox.  The loop is its
+//     own: it is audit_succ_stream's (rtla_kaudit.h), which k_pred_step runs,
+//     but inlined into that stream this kernel measured 3 % slower (DESIGN.md
+//     section 12).
 // Both count per invariant bit with ballots into wave-uniform registers, add
 // them to the block's LDS tally once per wave and to the device counters once
-// per block, and report the least violation key with one atomicMin per wave.
+// per block, and report the least violation key with one atomicMin per wave
+// (audit_finish).
 #include "rtla_kaudit.h"
 
 // Rows [0, n) of `cur`; masks (may be null): the violated mask of each row.
-// (A wave's counts are u32: a wave sees far fewer than 2^32 rows.)
 template <int NS>
 __global__ void __launch_bounds__(256)
 k_audit_state(Layout L, Ring cur, unsigned long long n, int tr, int* __restrict__ masks, AuditCounters* ctr) {
@@ -30,32 +29,9 @@ k_audit_state(Layout L, Ring cur, unsigned long long n, int tr, int* __restrict_
 
   unsigned int cnt[INV_COUNT] = {};
   unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
-  const unsigned long long ngroup = (n + 63) >> 6;
-  for (unsigned long long g = (unsigned long long)blockIdx.x * wpb + wave; g < ngroup;
-       g += (unsigned long long)gridDim.x * wpb) {
-    const int nv = (int)min<unsigned long long>(64ull, n - (g << 6));
-    for (int r0 = 0; r0 < nv; r0 += tr) {
-      const int nt = min(tr, nv - r0);
-      const unsigned long long first = (g << 6) + r0;
-      copy_words_lds16(tile, ring_row(cur, first, W), nt * W, lane);
-      wave_sync();
-      int bad = 0;
-      if (lane < nt) {
-        bad = check_invariants_v<NS>(L, (const uint32_t*)(tile + lane * W), -1, 0u, 0u, 0, 0u);
-        if (masks) masks[first + lane] = bad;
-      }
-      const unsigned long long mb = __ballot(bad != 0);
-      if (mb) {
-        audit_count(bad, cnt);
-        if (vkey == AUDIT_NO_VIOLATION) {  // groups and tiles ascend: the wave's first is its least
-          const int fl = __builtin_ctzll(mb);
-          vkey = audit_key(first + fl, 0, 1, __shfl(bad, fl));
-        }
-      }
-      evaluated += nt;
-      wave_sync();
-    }
-  }
+  audit_row_stream(cur, n, W, tr, tile, masks, cnt, evaluated, vkey, wave, wpb, lane, [&](const uint32_t* row) {
+    return check_invariants_v<NS>(L, row, -1, 0u, 0u, 0, 0u);
+  });
   audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
 }
 
@@ -98,7 +74,7 @@ k_audit_succ(Layout L, Ring cur, unsigned long long n, int* __restrict__ masks, 
       const unsigned long long mb = __ballot(bad != 0);
       if (mb) {
         all |= audit_count(bad, cnt);
-        if (!found) {  // the row's least violating instance: instances ascend with q
+        if (!found) {  // the row's least violating instance: instances ascend with the candidates
           found = true;
           const int fl = __builtin_ctzll(mb);
           const unsigned long long key = audit_key(s, __shfl(inst, fl), __shfl((int)d.in_model, fl), __shfl(bad, fl));

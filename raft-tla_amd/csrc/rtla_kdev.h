@@ -1,7 +1,7 @@
 // rtla_kdev.h -- the device helpers every kernel translation unit shares
 // (and the few host helpers of their launchers): wave and lane primitives,
 // LDS copies, ring stores, the fingerprint set, flags and violations,
-// next-level and outbox reservations, candidates and coverage, the
+// next-level and outbox reservations, a lane's candidate Delta, the
 // wave-per-state kernels' per-parent setup, SYMMETRY's successor accessors,
 // the compiled-in layouts.  The level kernel itself is rtla_klevel.h.
 #pragma once
@@ -315,28 +315,22 @@ __device__ __forceinline__ void overflow_put(const ShardBox& box, bool ov, FP f,
   }
 }
 
-// ---- candidates and coverage codes
+// ---- candidates (candidate_inst, cover_code: rtla_model.h)
 
-// Map the q-th candidate of a parent with `nmsg` bag slots to an instance id:
-// the fixed families first, then Receive / Duplicate / Drop over used slots.
-__device__ __forceinline__ int candidate_inst(const Layout& L, int q, int nmsg) {
-  const int fixed = L.fam[F_RECEIVE];
-  if (q < fixed) return q;
-  int r = q - fixed;
-  int fam = r / nmsg, slot = r - fam * nmsg;
-  return fam_base(L, F_RECEIVE + fam) + slot;
-}
-
-__device__ __forceinline__ int inst_family(const Layout& L, int inst) {
-  int fam = 0;
-#pragma unroll
-  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
-  return fam;
-}
-
-__device__ __forceinline__ int cover_code(const Layout& L, int inst, int sub) {
-  const int fam = inst_family(L, inst);
-  return fam == F_RECEIVE ? F_COUNT + sub : fam;
+// This lane's candidate q of a parent with `ncand` candidates and `nmsg` bag
+// slots: its instance and Delta (q >= ncand: instance 0, not enabled).  Returns
+// whether it is an enabled successor that counts (enabled_ok).
+template <int NS, class P>
+__device__ __forceinline__ bool candidate_delta(const Layout& L, P prow, int q, int ncand, int nmsg, int* flags,
+                                                int& inst, DeltaT<NS>& d) {
+  d.enabled = 0;
+  d.in_model = 0;
+  inst = 0;
+  if (q < ncand) {
+    inst = candidate_inst(L, q, nmsg);
+    compute_delta<NS>(L, prow, inst, d);
+  }
+  return enabled_ok(flags, d.enabled != 0, d.err);
 }
 
 // ---- per-parent setup of the wave-per-state kernels

@@ -1,6 +1,6 @@
 // rtla_kpred.hip -- user-defined predicates on the GPU: one compiled predicate
 // set (rtla_pred.h's bytecode) evaluated on a batch of rows or on the frontier
-// in HBM.  k_audit_state's memory shape (rtla_kaudit.hip): a wave takes 64
+// in HBM.  k_pred_state runs audit_row_stream (rtla_kaudit.h): a wave takes 64
 // consecutive rows, stages them (in tiles of `tr` rows) into LDS with 16-byte
 // loads, each lane interprets the program on its own row there, per-bit ballots
 // go into wave-uniform counts, the block's LDS tally and the device counters
@@ -52,45 +52,20 @@ k_pred_state(Layout L, Ring cur, unsigned long long n, int tr, const uint32_t* _
 
   unsigned int cnt[PRED_MAX_DEFS] = {};
   unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
-  const unsigned long long ngroup = (n + 63) >> 6;
-  for (unsigned long long g = (unsigned long long)blockIdx.x * wpb + wave; g < ngroup;
-       g += (unsigned long long)gridDim.x * wpb) {
-    const int nv = (int)min<unsigned long long>(64ull, n - (g << 6));
-    for (int r0 = 0; r0 < nv; r0 += tr) {
-      const int nt = min(tr, nv - r0);
-      const unsigned long long first = (g << 6) + r0;
-      copy_words_lds16(tile, ring_row(cur, first, W), nt * W, lane);
-      wave_sync();
-      int bad = 0;
-      if (lane < nt) {
-        int err = 0;
-        bad = pred_eval<NS>(L, (const uint32_t*)(tile + lane * W), (const uint32_t*)code, file, &err);
-        if (err) {
-          atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
-          bad = 0;
-        }
-        if (masks) masks[first + lane] = bad;
-      }
-      const unsigned long long mb = __ballot(bad != 0);
-      if (mb) {
-        audit_count(bad, cnt);
-        if (vkey == AUDIT_NO_VIOLATION) {  // groups and tiles ascend: the wave's first is its least
-          const int fl = __builtin_ctzll(mb);
-          vkey = pred_key(first + fl, __shfl(bad, fl));
-        }
-      }
-      evaluated += nt;
-      wave_sync();
-    }
-  }
+  audit_row_stream(cur, n, W, tr, tile, masks, cnt, evaluated, vkey, wave, wpb, lane, [&](const uint32_t* row) {
+    int err = 0;
+    const int bad = pred_eval<NS>(L, row, (const uint32_t*)code, file, &err);
+    if (err) atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
+    return err ? 0 : bad;
+  });
   audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
 }
 
 // ---- action properties: an action set on every step out of rows [0, n) of `cur`.
 //
-// k_audit_succ's shape (rtla_kaudit.hip): one wave per state, the parent in LDS (load_parent: with its new
-// allLogs words and the fingerprint they give), each lane the Delta of one candidate instance, the enabled lanes
-// ranked by ballot.  The interpreter reads rows, so the enabled children are materialised (parent + patches, as
+// k_pred_step runs audit_succ_stream (rtla_kaudit.h): one wave per state, the parent in LDS (load_parent: with its
+// new allLogs words and the fingerprint they give), each lane the Delta of one candidate instance, the enabled
+// lanes ranked by ballot.  The interpreter reads rows, so the enabled children are materialised (parent + patches, as
 // k_expand_batch's) into a per-wave LDS stage, `tc` at a time, and the lane whose child is in the stage runs
 // pred_eval_rows on (parent row, child row), both in LDS; the child never leaves the CU.  Per wave: parent
 // (even_words(W)) | allLogs' (32) | server hashes (4 * NMAX) | tc children at stride W | 1 (odd: the lanes' reads
@@ -132,61 +107,32 @@ k_pred_step(Layout L, Ring cur, unsigned long long n, int tc, const uint32_t* __
 
   unsigned int cnt[PRED_MAX_DEFS] = {};
   unsigned long long evaluated = 0, vkey = AUDIT_NO_VIOLATION;
-  const int fixed = L.fam[F_RECEIVE];
-  for (unsigned long long s = (unsigned long long)blockIdx.x * wpb + wave; s < n;
-       s += (unsigned long long)gridDim.x * wpb) {
-    const FP pfp = load_parent<NS>(L, ring_row(cur, s, W), prow, pall, hsrv, lane);
-    const int nmsg = row_nmsg(L, prow);
-    const int ncand = fixed + 3 * nmsg;
-    int all = 0;
-    bool found = false;
-    for (int base = 0; base < ncand; base += 64) {
-      const int q = base + lane;
-      DeltaT<NS> d;
-      d.enabled = 0;
-      d.in_model = 0;
-      int inst = 0;
-      if (q < ncand) {
-        inst = candidate_inst(L, q, nmsg);
-        compute_delta<NS>(L, prow, inst, d);
-      }
-      const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
-      const unsigned long long m = __ballot(en);
-      const int nen = __popcll(m);
-      if (!nen) continue;
-      evaluated += nen;
-      const int rank = __popcll(m & ((1ull << lane) - 1ull));
-      const FP cfp = en ? fp_add(pfp, delta_fp<NS>(L, prow, d, d.srv >= 0 ? &hsrv[d.srv] : nullptr)) : FP{0, 0};
-      int bad = 0;
-      for (int b = 0; b < nen; b += tc) {
-        if (en && rank >= b && rank < b + tc) {
-          uint32_t* const child = stage + (rank - b) * cs;
-          materialize<NS>(L, prow, d, pall, cfp, child);
-          int err = 0;
-          bad = pred_eval_rows<NS, true>(L, (const uint32_t*)prow, (const uint32_t*)child, (const uint32_t*)code,
-                                         files + (rank - b) * PRED_STRIDE, &err);
-          if (err) {
-            atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
-            bad = 0;
+  FP pfp{0, 0};  // the parent's fingerprint with allLogs' applied
+  audit_succ_stream<NS>(
+      L, n, prow, masks, cnt, evaluated, vkey, ctr, wave, wpb, lane,
+      [&](unsigned long long s) { pfp = load_parent<NS>(L, ring_row(cur, s, W), prow, pall, hsrv, lane); },
+      [&](bool en, unsigned long long m, int, const DeltaT<NS>& d) {
+        const int nen = __popcll(m);
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        const FP cfp = en ? fp_add(pfp, delta_fp<NS>(L, prow, d, d.srv >= 0 ? &hsrv[d.srv] : nullptr)) : FP{0, 0};
+        int bad = 0;
+        for (int b = 0; b < nen; b += tc) {
+          if (en && rank >= b && rank < b + tc) {
+            uint32_t* const child = stage + (rank - b) * cs;
+            materialize<NS>(L, prow, d, pall, cfp, child);
+            int err = 0;
+            bad = pred_eval_rows<NS, true>(L, (const uint32_t*)prow, (const uint32_t*)child, (const uint32_t*)code,
+                                           files + (rank - b) * PRED_STRIDE, &err);
+            if (err) {
+              atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
+              bad = 0;
+            }
+            if (step_stutters(prow, child)) bad = 0;  // (evaluated first, as [A]_vars: an error stays an error)
           }
-          if (step_stutters(prow, child)) bad = 0;  // (evaluated first, as [A]_vars: an error stays an error)
+          wave_sync();  // the next tile's lanes write the slots this tile's lanes read
         }
-        wave_sync();  // the next tile's lanes write the slots this tile's lanes read
-      }
-      const unsigned long long mb = __ballot(bad != 0);
-      if (mb) {
-        all |= audit_count(bad, cnt);
-        if (!found) {  // the row's least false instance: instances ascend with q
-          found = true;
-          const int fl = __builtin_ctzll(mb);
-          const unsigned long long key = step_key(s, __shfl(inst, fl), __shfl((int)d.in_model, fl), __shfl(bad, fl));
-          if (key < vkey) vkey = key;
-        }
-      }
-    }
-    if (masks && lane == 0) masks[s] = all;
-    wave_sync();
-  }
+        return bad;
+      });
   audit_finish(lds, cnt, evaluated, vkey, ctr, lane);
 }
 

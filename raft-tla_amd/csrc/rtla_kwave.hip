@@ -37,15 +37,9 @@ k_expand(Layout L, Ring cur, unsigned long long s_begin, unsigned long long s_en
     const int nmsg = row_nmsg(L, prow);
     const int ncand = fixed + 3 * nmsg;
     for (int base = 0; base < ncand; base += 64) {
-      const int q = base + lane;
       DeltaT<NS> d;
-      d.enabled = 0;
-      int inst = 0;
-      if (q < ncand) {
-        inst = candidate_inst(L, q, nmsg);
-        compute_delta<NS>(L, prow, inst, d);
-      }
-      const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
+      int inst;
+      const bool en = candidate_delta<NS>(L, prow, base + lane, ncand, nmsg, &ctr->flags, inst, d);
       my_gen += en ? 1 : 0;
       bool isnew = false;
       FP cfp{0, 0};

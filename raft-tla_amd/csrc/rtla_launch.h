@@ -85,11 +85,11 @@ struct AuditCounters;
 hipError_t launch_audit(const Layout& L, const Ring& cur, uint64_t n, int succ, int* masks, AuditCounters* ctr,
                         hipStream_t st);
 // A compiled predicate set (rtla_kpred.hip, rtla_pred.h) on rows [0, n) of `cur`: prog, nwords program words in
-// device memory; masks and ctr as launch_audit's (bit k = definition k; the key is pred_key).
+// device memory; masks and ctr as launch_audit's (bit k = definition k).
 hipError_t launch_pred(const Layout& L, const Ring& cur, uint64_t n, const uint32_t* prog, int nwords, int* masks,
                        AuditCounters* ctr, hipStream_t st);
 // A compiled action set on every step (row, enabled successor) out of rows [0, n) of `cur` (k_pred_step): masks
-// the OR over each row's steps; the key is step_key.
+// the OR over each row's steps; the key carries the step's instance.
 hipError_t launch_pred_step(const Layout& L, const Ring& cur, uint64_t n, const uint32_t* prog, int nwords,
                             int* masks, AuditCounters* ctr, hipStream_t st);
 hipError_t launch_insert_remote(const uint64_t* recv_fp, const uint64_t* counts, int nshard, uint64_t cap,

@@ -239,6 +239,31 @@ RTLA_HD int log_off_at(const Layout& L, int n) {
   return r;
 }
 
+// ---- candidates and coverage codes
+// Map the q-th candidate of a parent with `nmsg` bag slots to an instance id:
+// the fixed families first, then Receive / Duplicate / Drop over used slots.
+// Instances ascend with q.
+RTLA_HD int candidate_inst(const Layout& L, int q, int nmsg) {
+  const int fixed = L.fam[F_RECEIVE];
+  if (q < fixed) return q;
+  int r = q - fixed;
+  int fam = r / nmsg, slot = r - fam * nmsg;
+  return fam_base(L, F_RECEIVE + fam) + slot;
+}
+
+RTLA_HD int inst_family(const Layout& L, int inst) {
+  int fam = 0;
+#pragma unroll
+  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
+  return fam;
+}
+
+// Coverage code (COVER_CODES, rtla_device.h): the family, Receive split by sub-action.
+RTLA_HD int cover_code(const Layout& L, int inst, int sub) {
+  const int fam = inst_family(L, inst);
+  return fam == F_RECEIVE ? F_COUNT + sub : fam;
+}
+
 // ------------------------------------------------------------- fields ----
 RTLA_HD uint32_t s_term(uint32_t w) { return w & 15u; }
 RTLA_HD uint32_t s_role(uint32_t w) { return (w >> 4) & 3u; }

@@ -1,11 +1,8 @@
 // rtla_predhost.cpp -- user-defined predicates: the rtla_pred_* ABI.  The
 // compiler is rtla_pred.cpp (host only), the interpreter rtla_pred.h -- run
 // here per row by rtla_pred_replay, and by the kernel of rtla_kpred.hip for
-// rtla_pred_batch and rtla_pred_frontier, which are the audit's batch and
-// frontier passes (rtla_audit.cpp) with that kernel.
-#include <atomic>
-#include <thread>
-
+// rtla_pred_batch and rtla_pred_frontier, which are the batch and frontier
+// passes of rtla_audit.cpp with that kernel.
 #include "rtla_ctx.h"
 #include "rtla_predc.h"
 #include "rtla_step.h"
@@ -60,38 +57,6 @@ static int pred_layout(const rtla_cfg* c, const rtla_pred* p, bool step, Layout*
   return p && p->step == step && pred_bound_to(p, *L) ? RTLA_OK : RTLA_E_ARG;
 }
 
-// The host replay of both kinds: row(k, tally) evaluates row k into the thread's tally and returns its mask.
-template <class F>
-static int replay_rows(size_t n, int threads, int32_t* masks, uint64_t* counts, uint64_t* evaluated, F row) {
-  const int nt = (int)std::min<size_t>((size_t)std::min(text_threads(threads), 16), std::max<size_t>(1, n / 256));
-  std::vector<AuditCounters> part((size_t)nt, audit_zero());
-  std::atomic<size_t> next{0};
-  auto work = [&](int t) {
-    AuditCounters& tl = part[(size_t)t];
-    for (;;) {
-      const size_t b = next.fetch_add(256);
-      if (b >= n) break;
-      for (size_t k = b; k < std::min(n, b + 256); k++) masks[k] = row(k, tl);
-    }
-  };
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
-  work(0);
-  for (auto& th : pool) th.join();
-  int flags = 0;
-  uint64_t sum[AUDIT_COUNTS] = {}, ev = 0;
-  for (const AuditCounters& q : part) {
-    flags |= q.flags;
-    ev += q.evaluated;
-    for (int k = 0; k < AUDIT_COUNTS; k++) sum[k] += q.counts[k];
-  }
-  if (flags) return flags_to_status(flags);
-  if (counts)
-    for (int k = 0; k < AUDIT_COUNTS; k++) counts[k] = sum[k];
-  if (evaluated) *evaluated = ev;
-  return RTLA_OK;
-}
-
 extern "C" int rtla_pred_replay(const rtla_cfg* c, const rtla_pred* p, const uint32_t* rows, size_t n, int threads,
                                 int32_t* masks, uint64_t* counts) {
   Layout L;
@@ -105,7 +70,7 @@ extern "C" int rtla_pred_replay(const rtla_cfg* c, const rtla_pred* p, const uin
       tl.flags |= FLAG_SPEC_ERROR;
       return 0;
     }
-    for (int d = 0; d < PRED_MAX_DEFS; d++) tl.counts[d] += bad >> d & 1;
+    audit_tally(tl, k, 0, 1, bad);
     return bad;
   });
 }
@@ -154,19 +119,16 @@ extern "C" int rtla_pred_step_batch(const rtla_cfg* c, const rtla_pred* p, const
 
 static int pred_frontier(rtla_ctx* x, const rtla_pred* p, bool step, rtla_audit_stats* out) {
   if (!x || !p) return RTLA_E_ARG;
-  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
-      x->sh[0].n_cur == 0)
-    return RTLA_E_STATE;
+  if (!frontier_pass_ok(x)) return RTLA_E_STATE;
   const Layout L = x->L;
   if (p->step != step || !pred_bound_to(p, L)) return RTLA_E_ARG;
   HIPCHK(hipSetDevice(x->device));
   AuditState& a = x->audit;
   if (!a.prog) HIPCHK(hipMalloc((void**)&a.prog, PRED_MAX_WORDS * sizeof(uint32_t)));
   HIPCHK(hipMemcpyAsync(a.prog, p->code.data(), p->code.size() * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
-  return audit_frontier(x, step, step ? AUDIT_PRED_STEP : AUDIT_PRED_STATE,
-                        [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
-                          return pred_launcher(p)(L, cur, n, a.prog, (int)p->code.size(), m, ctr, st);
-                        }, out);
+  return audit_frontier(x, step, [&](const Ring& cur, uint64_t n, int* m, AuditCounters* ctr, hipStream_t st) {
+    return pred_launcher(p)(L, cur, n, a.prog, (int)p->code.size(), m, ctr, st);
+  }, out);
 }
 
 extern "C" int rtla_pred_frontier(rtla_ctx* x, const rtla_pred* p, rtla_audit_stats* out) {

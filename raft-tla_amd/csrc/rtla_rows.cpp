@@ -117,33 +117,23 @@ static uint64_t fnv1a64_sum(char* const* txt, const size_t* len, int m) {
 uint64_t rows_digest(const Layout& L, const uint32_t* rows, size_t n, int threads, bool orbit) {
   threads = (int)std::min<size_t>((size_t)threads, std::max<size_t>(1, n / 4096));
   std::vector<uint64_t> part((size_t)threads, 0);
-  std::atomic<size_t> next{0};
   const size_t cap = state_text_cap(L);
-  auto work = [&](int t) {
+  parallel_chunks(n, 8192, threads, [&](int t, size_t b, size_t e) {
     std::vector<char> buf((TEXT_ILP + 1) * cap);  // TEXT_ILP texts + one scratch area
     char* txt[TEXT_ILP];
     size_t len[TEXT_ILP];
     for (int i = 0; i < TEXT_ILP; i++) txt[i] = buf.data() + i * cap;
     char* scratch = buf.data() + TEXT_ILP * cap;
     uint64_t acc = 0;
-    for (;;) {
-      const size_t b = next.fetch_add(8192);
-      if (b >= n) break;
-      const size_t e = std::min(n, b + 8192);
-      for (size_t k = b; k < e; k += TEXT_ILP) {
-        const int m = (int)std::min<size_t>(TEXT_ILP, e - k);
-        for (int i = 0; i < m; i++)
-          len[i] = orbit ? state_orbit_text_into(L, rows + (k + i) * (size_t)L.W, txt[i], scratch)
-                         : state_text_into(L, rows + (k + i) * (size_t)L.W, txt[i], scratch);
-        acc += fnv1a64_sum(txt, len, m);
-      }
+    for (size_t k = b; k < e; k += TEXT_ILP) {
+      const int m = (int)std::min<size_t>(TEXT_ILP, e - k);
+      for (int i = 0; i < m; i++)
+        len[i] = orbit ? state_orbit_text_into(L, rows + (k + i) * (size_t)L.W, txt[i], scratch)
+                       : state_text_into(L, rows + (k + i) * (size_t)L.W, txt[i], scratch);
+      acc += fnv1a64_sum(txt, len, m);
     }
-    part[(size_t)t] = acc;
-  };
-  std::vector<std::thread> pool;
-  for (int t = 1; t < threads; t++) pool.emplace_back(work, t);
-  work(0);
-  for (auto& th : pool) th.join();
+    part[(size_t)t] += acc;
+  });
   uint64_t sum = 0;
   for (uint64_t v : part) sum += v;
   return sum;

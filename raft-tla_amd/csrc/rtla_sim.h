@@ -20,7 +20,7 @@
 // (sum mod 2^64 of sim_path_term over the states entered) | steps taken |
 // stop code << 32.
 #pragma once
-#include "rtla_device.h"
+#include "rtla_audit.h"
 #include "rtla_synth.h"
 
 namespace rtla {
@@ -60,12 +60,6 @@ RTLA_HD int sim_key_step(uint64_t key) { return (int)(key >> 22 & 0xffff); }
 RTLA_HD int sim_key_inst(uint64_t key) { return (int)(key >> 6 & 0xffff); }
 RTLA_HD int sim_key_in_model(uint64_t key) { return (int)(key >> 5 & 1); }
 RTLA_HD int sim_key_mask(uint64_t key) { return (int)(key & INV_ALL); }
-
-RTLA_HD int sim_cover_code(const Layout& L, int inst, int sub) {  // the level kernels' cover_code
-  int fam = 0;
-  for (int f = 1; f < F_COUNT; f++) fam += inst >= L.fam[f];
-  return fam == F_RECEIVE ? F_COUNT + sub : fam;
-}
 
 // Device counters of one rtla_simulate batch.
 struct SimCounters {
@@ -110,27 +104,11 @@ static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uin
   SimEnd e{};
   e.stop = SIM_STOP_DEPTH;
   e.viol_inst = -1;
-  const int fixed = L.fam[F_RECEIVE];
   for (int t = 1; t <= depth; t++) {
     const FP pfp = fp_add(row_fp(cur), alllogs_delta<NS>(L, cur, pall));
-    const int nmsg = row_nmsg(L, cur);
-    const int ncand = fixed + 3 * nmsg;
-    auto inst_of = [&](int q) {
-      if (q < fixed) return q;
-      const int r = q - fixed, fam = r / nmsg;
-      return fam_base(L, F_RECEIVE + fam) + (r - fam * nmsg);
-    };
     uint32_t total = 0;  // |M|; model[]: its instances, ascending
     bool violated = false;
-    DeltaT<NR> d;
-    for (int q = 0; q < ncand; q++) {
-      const int inst = inst_of(q);
-      compute_delta<NS>(L, cur, inst, d);
-      if (!d.enabled) continue;
-      if (d.err) {
-        tl.flags |= d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW;
-        continue;
-      }
+    for_each_successor<NS>(L, cur, tl.flags, [&](int inst, const auto& d) {
       tl.generated++;
       const int bad = check_invariants_v<NS>(L, cur, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
       if (bad && !violated) {
@@ -140,7 +118,7 @@ static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uin
         materialize<NS>(L, cur, d, pall, cfp, nxt);
       }
       if (d.in_model) model[total++] = (uint16_t)inst;
-    }
+    });
     if (violated) {
       e.stop = SIM_STOP_VIOLATION;
       const uint64_t key = sim_viol_key(rel_walk, (uint32_t)t, e.viol_inst, e.viol_in_model, e.viol_mask);
@@ -155,11 +133,12 @@ static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uin
     }
     {
       const int inst = model[sim_draw(base, (uint32_t)t, total)];
+      DeltaT<NR> d;
       compute_delta<NS>(L, cur, inst, d);
       const FP cfp = fp_add(pfp, delta_fp<NS>(L, cur, d));
       materialize<NS>(L, cur, d, pall, cfp, nxt);
       e.digest += sim_path_term(cfp, (uint32_t)t);
-      tl.taken[sim_cover_code(L, inst, d.sub)]++;
+      tl.taken[cover_code(L, inst, d.sub)]++;
       tl.steps++;
       e.length = (uint32_t)t;
       on_state(t, (const uint32_t*)nxt, (int32_t)(d.sub << 16 | inst), false);

@@ -3,9 +3,6 @@
 // computed on the host by sim_walk_serial: rtla_sim_replay / rtla_sim_walk
 // (stateless, no GPU), and the counterexample of a simulated violation
 // (rtla_trace).
-#include <atomic>
-#include <thread>
-
 #include "rtla_ctx.h"
 #include "rtla_sim.h"
 
@@ -73,30 +70,20 @@ extern "C" int rtla_sim_replay(const rtla_cfg* c, const uint32_t* start_rows, si
   for (uint64_t b0 = 0; b0 < n_walks && sum.viol_key == SIM_NO_VIOLATION; b0 += SIM_BATCH) {
     const uint64_t nb = std::min<uint64_t>(SIM_BATCH, n_walks - b0);
     std::vector<SimTally> part((size_t)nt);
-    std::atomic<uint64_t> next{0};
-    auto work = [&](int t) {
+    parallel_chunks(nb, 64, nt, [&](int t, size_t i0, size_t i1) {
       std::vector<uint32_t> buf(2 * (size_t)L.W);
-      SimTally& tl = part[(size_t)t];
-      for (;;) {
-        const uint64_t i0 = next.fetch_add(64);
-        if (i0 >= nb) break;
-        for (uint64_t i = i0; i < std::min(nb, i0 + 64); i++) {
-          const uint64_t w = first_walk + b0 + i;
-          const SimEnd e = dispatch_n(L, [&](auto ns) {
-            return sim_walk_serial<decltype(ns)::value>(L, start_rows + (w % n_start) * (size_t)L.W, seed, w, i, depth,
-                                                        buf.data(), tl, [](int, const uint32_t*, int32_t, bool) {});
-          });
-          if (ends) {
-            uint64_t* o = ends + 4 * (b0 + i);
-            o[0] = e.last.a; o[1] = e.last.b; o[2] = e.digest; o[3] = sim_end_word(e.length, e.stop);
-          }
+      for (uint64_t i = i0; i < i1; i++) {
+        const uint64_t w = first_walk + b0 + i;
+        const SimEnd e = dispatch_n(L, [&](auto ns) {
+          return sim_walk_serial<decltype(ns)::value>(L, start_rows + (w % n_start) * (size_t)L.W, seed, w, i, depth,
+                                                      buf.data(), part[(size_t)t], [](int, const uint32_t*, int32_t, bool) {});
+        });
+        if (ends) {
+          uint64_t* o = ends + 4 * (b0 + i);
+          o[0] = e.last.a; o[1] = e.last.b; o[2] = e.digest; o[3] = sim_end_word(e.length, e.stop);
         }
       }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; t++) pool.emplace_back(work, t);
-    work(0);
-    for (auto& th : pool) th.join();
+    });
     for (const SimTally& p : part) {
       sum.steps += p.steps; sum.generated += p.generated; sum.stuck += p.stuck; sum.flags |= p.flags;
       sum.viol_key = std::min(sum.viol_key, p.viol_key);
@@ -113,9 +100,7 @@ extern "C" int rtla_sim_replay(const rtla_cfg* c, const uint32_t* start_rows, si
 extern "C" int rtla_simulate(rtla_ctx* x, uint64_t seed, uint64_t first_walk, uint64_t n_walks, int32_t depth,
                              uint64_t* ends, rtla_sim_stats* out) {
   if (!x) return RTLA_E_ARG;
-  if (x->cfg.mode == RTLA_MODE_DEDUP || x->world != 1 || x->nshard != 1 || !x->inited || x->viol_shard() ||
-      x->sh[0].n_cur == 0)
-    return RTLA_E_STATE;
+  if (!frontier_pass_ok(x)) return RTLA_E_STATE;
   if (depth < 0 || depth > SIM_MAX_DEPTH || first_walk + n_walks < first_walk) return RTLA_E_ARG;
   const Layout& L = x->L;
   if (!sim_layout_ok(L)) return RTLA_E_CONFIG;

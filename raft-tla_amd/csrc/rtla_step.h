@@ -1,8 +1,7 @@
-// rtla_step.h -- action properties on the host: one row's enabled successors
-// enumerated as the audit's successor mode does (audit_row_serial, rtla_audit.h),
-// each materialised and the action program run on (row, successor).  The kernel
-// k_pred_step (rtla_kpred.hip) computes the same masks, counts and key.
-// Semantics: DESIGN.md section 14.
+// rtla_step.h -- action properties on the host: each enabled successor of a row
+// (for_each_successor, rtla_audit.h) materialised and the action program run on
+// (row, successor).  The kernel k_pred_step (rtla_kpred.hip) computes the same
+// masks, counts and key.  Semantics: DESIGN.md section 14.
 #pragma once
 #include "rtla_audit.h"
 #include "rtla_pred.h"
@@ -19,40 +18,23 @@ RTLA_HD bool step_stutters(P s, Q t) {
 template <int NS>
 static inline int step_row_serial(const Layout& L, const uint32_t* row, uint64_t index, const uint32_t* prog,
                                   AuditCounters& t) {
-  constexpr int NR = NS ? NS : NMAX;
   uint32_t pall[33], child[WMAX];
   int file[PRED_FILE];
   const FP pfp = fp_add(row_fp(row), alllogs_delta<NS>(L, row, pall));
-  const int fixed = L.fam[F_RECEIVE], nmsg = row_nmsg(L, row), ncand = fixed + 3 * nmsg;
   int all = 0;
-  DeltaT<NR> d;
-  for (int q = 0; q < ncand; q++) {  // the level kernels' candidates: instances ascend with q
-    int inst = q;
-    if (q >= fixed) {
-      const int r = q - fixed, fam = r / nmsg;
-      inst = fam_base(L, F_RECEIVE + fam) + (r - fam * nmsg);
-    }
-    compute_delta<NS>(L, row, inst, d);
-    if (!d.enabled) continue;
-    if (d.err) {
-      t.flags |= d.err == 1 ? FLAG_SPEC_ERROR : FLAG_ROW_OVERFLOW;
-      continue;
-    }
+  for_each_successor<NS>(L, row, t.flags, [&](int inst, const auto& d) {
     materialize<NS>(L, row, d, pall, fp_add(pfp, delta_fp<NS>(L, row, d)), child);
     t.evaluated++;
     int err = 0;
     int bad = pred_eval_rows<NS, true>(L, row, (const uint32_t*)child, prog, file, &err);  // evaluated first, as [A]_vars
     if (err) {
       t.flags |= FLAG_SPEC_ERROR;
-      continue;
+      return;
     }
     if (step_stutters(row, child)) bad = 0;
-    if (!bad) continue;
-    for (int k = 0; k < AUDIT_COUNTS; k++) t.counts[k] += bad >> k & 1;
-    const uint64_t key = step_key(index, inst, d.in_model, bad);
-    if (key < t.viol_key) t.viol_key = key;
+    audit_tally(t, index, inst, d.in_model, bad);
     all |= bad;
-  }
+  });
   return all;
 }
 

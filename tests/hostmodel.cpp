@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "rtla_audit.h"
 #include "rtla_device.h"
 #include "rtla_model.h"
 #include "rtla_plan.h"
@@ -68,6 +69,16 @@ void hm_record_fields(int kind, uint64_t r, uint64_t* out) {
   out[0] = kind == 0 ? parent_shard(r) : kind == 1 ? successor_input(r) : outbox_parent(r);
   out[1] = kind == 0 ? parent_index(r) : kind == 1 ? (uint64_t)successor_label(r) : (uint64_t)outbox_inst(r);
   out[2] = kind == 0 ? (uint64_t)parent_inst(r) : kind == 1 ? (uint64_t)successor_inst(r) : 0;
+}
+
+// The violation key of the passes over rows (rtla_audit.h).  hm_audit_key_fields: the accessors' view of key,
+// in out[0..3] (index, instance, in_model, mask).
+uint64_t hm_audit_key(uint64_t index, int inst, int in_model, int mask) { return audit_key(index, inst, in_model, mask); }
+void hm_audit_key_fields(uint64_t key, uint64_t* out) {
+  out[0] = audit_key_index(key);
+  out[1] = (uint64_t)audit_key_inst(key);
+  out[2] = (uint64_t)audit_key_in_model(key);
+  out[3] = (uint64_t)audit_key_mask(key);
 }
 
 // Fingerprint of a row from scratch.

@@ -18,7 +18,8 @@ def lib():
     global _lib
     if _lib is None:
         deps = [SRC, os.path.join(ROOT, "include", "rtla.h")] + [os.path.join(CSRC, h) for h in
-                                                                 ("rtla_model.h", "rtla_plan.h", "rtla_device.h")]
+                                                                 ("rtla_model.h", "rtla_plan.h", "rtla_device.h",
+                                                                  "rtla_audit.h")]
         if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(OUT), exist_ok=True)
             subprocess.check_call(["g++", "-O2", "-std=c++20", "-shared", "-fPIC", "-I", CSRC, "-o", OUT + ".tmp", SRC])
@@ -38,6 +39,10 @@ def lib():
         _lib.hm_record.restype = C.c_uint64
         _lib.hm_record_fields.argtypes = [C.c_int, C.c_uint64, u64s]
         _lib.hm_record_fields.restype = None
+        _lib.hm_audit_key.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int]
+        _lib.hm_audit_key.restype = C.c_uint64
+        _lib.hm_audit_key_fields.argtypes = [C.c_uint64, u64s]
+        _lib.hm_audit_key_fields.restype = None
     return _lib
 
 

@@ -85,6 +85,8 @@ def test_frontier_audit_in_place():
         assert res.status == rtla.VIOLATION and res.counts == counts and res.audited == res.evaluated == len(front)
         assert 0 < counts["NoCandidate"] < len(front) and counts["AlwaysTrue"] == 0 and len(set(masks)) > 3
         first = next(k for k, m in enumerate(masks) if m)
+        # 258 rows: two blocks (four waves of 64 rows each), both with false rows; the least of them is reported
+        assert len(front) > 256 and any(masks[:256]) and any(masks[256:])
         assert (res.viol_index, res.viol_mask, res.viol_inst, res.viol_in_model) == (first, masks[first], -1, True)
         assert res.violation == preds.names_of(masks[first])
         assert ck.violation() == (", ".join(res.violation), True)

@@ -108,6 +108,8 @@ def test_audit_finds_a_violation_the_search_did_not_look_for():
         front = ck.frontier_flat()
         bad = two_leaders(cfg, front)
         assert bad, "level 19 holds a state with two leaders (golden n3_v1_t3_l1_m1_ntl)"
+        # several, found by different blocks (four waves of 64 rows each): the least of them is the one reported
+        assert len({k // 256 for k in bad}) > 1 and bad[0] // 256 < bad[-1] // 256
         res = ck.audit(("NoTwoLeaders",))
         assert res.status == rtla.VIOLATION and res.violation == ["NoTwoLeaders"]
         assert res.counts["NoTwoLeaders"] == len(bad) and res.audited == ck.frontier_size()
@@ -139,6 +141,8 @@ def test_successor_audit_reports_the_violating_successor():
         front = ck.frontier_flat()
         masks, counts = rtla.check_replay(cfg, front, ("NoTwoLeaders",), succ=True)
         first = next(k for k, m in enumerate(masks) if m)
+        # several rows with a violating successor, found by different blocks (four states each): the least is reported
+        assert len({k // 4 for k, m in enumerate(masks) if m}) > 1
         res = ck.audit(("NoTwoLeaders",), succ=True)
         assert res.status == rtla.VIOLATION and res.violation == ["NoTwoLeaders"]
         assert res.counts == counts and res.viol_index == first and res.audited == len(masks) < res.evaluated

@@ -6,6 +6,7 @@ succ=0) and on successors evaluated as parent + delta (check_replay succ=1
 against the predicates over raft_values.next_states)."""
 import pytest
 
+import hostmodel
 import limits
 import raft_values as rv
 import rtla
@@ -225,6 +226,42 @@ def test_value_oracle_bfs_finds_no_violation(monkeypatch):
     monkeypatch.setitem(rv.INVARIANTS, "LeaderCompleteness", leader_completeness)
     res = rv.bfs(rv.Cfg(2, 1, 3, 1, 1, ("ElectionSafety", "LogMatching", "StateMachineSafety", "LeaderCompleteness"), 1))
     assert res.violation is None and res.distinct == 25164
+
+
+# ---- the violation key of every pass over rows (rtla_audit.h audit_key), through tests/hostmodel.cpp
+
+IDX39 = (1 << 39) - 1
+
+
+def _key_fields(key):
+    out = (hostmodel.C.c_uint64 * 4)()
+    hostmodel.lib().hm_audit_key_fields(key, out)
+    return tuple(out)
+
+
+def test_the_one_violation_key_round_trips_and_orders_by_row_then_instance():
+    """index << 25 | instance << 9 | in_model << 8 | mask at the limits of every field (index 2^39 - 1, instance
+    65535, mask 255, both in_model values); the accessors invert it; the least key is the least row's, and within
+    a row the least instance's, whatever in_model and the mask are."""
+    enc = hostmodel.lib().hm_audit_key
+    indexes, insts, masks = (0, 1, 12345, IDX39 - 1, IDX39), (0, 1, 63, 64, 65534, 65535), (0, 1, 31, 128, 255)
+    for index in indexes:
+        for inst in insts:
+            for im in (0, 1):
+                for mask in masks:
+                    key = enc(index, inst, im, mask)
+                    assert key == index << 25 | inst << 9 | im << 8 | mask < 1 << 64
+                    assert _key_fields(key) == (index, inst, im, mask)
+    low = [(im, mask) for im in (0, 1) for mask in masks]
+    for index in indexes:
+        for a in insts:
+            for b in insts:
+                for la in low:
+                    for lb in low:
+                        if a != b:  # (one key per (row, instance): equal instances are the same step)
+                            assert (enc(index, a, *la) < enc(index, b, *lb)) == (a < b)
+    for index in indexes[:-1]:  # any key of row i is below any key of row i + 1
+        assert max(enc(index, 65535, im, mask) for im, mask in low) < min(enc(index + 1, 0, im, mask) for im, mask in low)
 
 
 def test_bad_arguments():

@@ -103,6 +103,8 @@ def test_frontier_steps_in_place():
         assert (res.audited, res.evaluated) == (len(front), evaluated)
         assert [counts[n] for n in LAWS] == [0] * 5 and counts["TermsFrozen"] > 0 and len(set(masks)) > 1
         first = next(k for k, m in enumerate(masks) if m)
+        # 840 rows, many of them with a false step, found by different blocks (four states each): the least is reported
+        assert len(front) > 256 and len({k // 4 for k, m in enumerate(masks) if m}) > 1
         # the least false instance of that row, from the Python functions over the row's successors in instance order
         s = tla_text.parse_state(vc, rtla.state_text(cfg, front[first]))
         inst, mask, in_model = next(
