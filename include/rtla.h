@@ -16,6 +16,8 @@
  *                            allocation (the `states/` dir, reference
  *                            .gitignore:2).
  *   rtla_init                "Computing initial states" -- Init (raft.tla:155-160).
+ *   rtla_init_rows           an INIT override (TLC: `INIT MyInit` in the cfg), restricted
+ *                            to explicit states: the search starts from given rows.
  *   rtla_step                one BFS level of TLC's worker loop: Next
  *                            (raft.tla:454-465), fingerprint, FPSet.put,
  *                            INVARIANT check (raft.cfg:3), enqueue.
@@ -70,7 +72,7 @@
 extern "C" {
 #endif
 
-#define RTLA_ABI_VERSION 11
+#define RTLA_ABI_VERSION 12
 
 /* status codes */
 #define RTLA_OK 0
@@ -156,6 +158,23 @@ int rtla_comm_id(void *out128);
 
 /* BFS. */
 int rtla_init(rtla_ctx *ctx, rtla_level_stats *out);
+/* rtla_init with level 1 being the n given rows (the roots) instead of Init:
+ * the seeded search.  Preconditions as rtla_init's; world == 1 (any number of
+ * virtual shards), else RTLA_E_STATE; n == 0 or rows == NULL: RTLA_E_ARG; roots
+ * that do not fit a shard's frontier: RTLA_E_OVERFLOW; a row whose message or
+ * election count exceeds the layout's: RTLA_E_ARG.  The rows' first four
+ * words (the stored fingerprint) are not trusted: they are recomputed as the
+ * level kernel stores them for a generated state.  Roots equal by the seen-set
+ * key (the fingerprint; under SYMMETRY the orbit key) count once, the first
+ * occurrence kept: out->new_states = distinct roots, out->generated = n.  Each
+ * root lives on the shard that owns its key, in the given order.  Every
+ * distinct root is checked against the configuration's invariants as Init is;
+ * the least violating root ends the search with RTLA_VIOLATION and is the
+ * whole trace (label -1).  A trace of the seeded search starts at the root the
+ * violation descends from ("Init first" below reads "that root first").
+ * rtla_checkpoint of a seeded search returns RTLA_E_STATE: a checkpoint does
+ * not hold the roots.  rtla_reset forgets them. */
+int rtla_init_rows(rtla_ctx *ctx, const uint32_t *rows, size_t n, rtla_level_stats *out);
 /* Forget the search (clear the fingerprint set, frontier, counters) but keep
  * the allocations, so the same model can be checked again from Init. */
 int rtla_reset(rtla_ctx *ctx);
@@ -165,7 +184,8 @@ int rtla_violation(rtla_ctx *ctx, int32_t *inv_mask, int32_t *in_model);
  * write the search (fingerprint set, parent records, current frontier,
  * counters) between levels to <prefix>.shard<id>.rtla, one file per shard
  * held by this context; recover it into a context opened with the same
- * configuration, then continue with rtla_step.  Collective when world > 1. */
+ * configuration, then continue with rtla_step.  Collective when world > 1.
+ * A search seeded with rtla_init_rows cannot be checkpointed: RTLA_E_STATE. */
 int rtla_checkpoint(rtla_ctx *ctx, const char *prefix);
 int rtla_recover(rtla_ctx *ctx, const char *prefix);
 /* Counterexample, Init first.  rows: n * rtla_row_words() u32; labels: action

@@ -58,7 +58,7 @@ std::string ckpt_path(const char* prefix, int shard) {
 // error is every rank's error and no rank is left waiting in a collective.
 extern "C" int rtla_checkpoint(rtla_ctx* x, const char* prefix) {
   if (!x || !prefix) return RTLA_E_ARG;
-  if (!x->inited) return RTLA_E_STATE;
+  if (!x->inited || x->seeded) return RTLA_E_STATE;  // (the files hold no roots: a seeded search stays in memory)
   std::vector<char> buf(64 << 20);
   // Each shard is written to <path>.tmp (flushed to disk); only when every
   // shard of every rank has been written are the files renamed over the
@@ -156,8 +156,9 @@ extern "C" int rtla_recover(rtla_ctx* x, const char* prefix) {
   } else if (err) {
     return err;
   }
-  x->init_row.assign(x->L.W, 0);
-  row_init(x->L, x->init_row.data());
+  x->roots.assign(x->L.W, 0);
+  row_init(x->L, x->roots.data());
+  x->seeded = false;
   x->inited = true;
   x->sim.viol = false;
   return RTLA_OK;

@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cstdio>
 #include <functional>
+#include <set>
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -124,7 +125,9 @@ struct rtla_ctx {
   uint64_t distinct = 0, generated = 0;
   uint64_t max_front = 0;  // largest frontier of any shard in the job (multi-shard round count)
   int grid = 0;
-  std::vector<uint32_t> init_row;
+  std::vector<uint32_t> roots;  // [n][W] the search's roots, each named by its parent record (root_record): Init
+                                // alone, or the distinct rows rtla_init_rows was given
+  bool seeded = false;          // the roots are rtla_init_rows's (no checkpoint holds them)
   SimState sim;
   AuditState audit;
 
@@ -146,6 +149,12 @@ inline bool frontier_pass_ok(rtla_ctx* x) {
   return x->cfg.mode != RTLA_MODE_DEDUP && x->world == 1 && x->nshard == 1 && x->inited && !x->viol_shard() &&
          x->sh[0].n_cur != 0;
 }
+
+// Parent record of root k of a search: the root mark -- shard byte 0xFF and instance 0xFFFF, which no stored
+// successor carries -- around an index field that counts down from 2^40 - 1, so root 0 (Init) keeps ~0ull.
+inline uint64_t root_record(uint64_t k) { return ~0ull - (k << 16); }
+inline bool is_root_record(uint64_t p) { return parent_shard(p) == 0xFF && parent_inst(p) == 0xFFFF; }
+inline uint64_t root_of(uint64_t p) { return (1ull << 40) - 1 - parent_index(p); }
 
 // A failing HIP call is reported and ends the function with `ret`.
 #define HIPCHK_RET(x, ret)                                                                          \

@@ -395,44 +395,119 @@ extern "C" int rtla_reset(rtla_ctx* x) {
   x->inited = false; x->finished = false; x->level = 0; x->distinct = 0; x->generated = 0; x->max_front = 0;
   x->sim.viol = false;
   x->audit.viol = false;
+  x->roots.clear();
+  x->seeded = false;
   return RTLA_OK;
 }
 
-extern "C" int rtla_init(rtla_ctx* x, rtla_level_stats* st) {
-  if (!x) return RTLA_E_ARG;
-  if (x->inited || x->cfg.mode == RTLA_MODE_DEDUP) return RTLA_E_STATE;
-  double t0 = now_s();
+// Level 1 of a search: the n rows of `rows` (Init alone, or rtla_init_rows's) become its roots.  Each gets the
+// fingerprint a generated state carries (its own, from scratch) and a seen-set key: that fingerprint -- or, for
+// the rows of a seeded SYMMETRY search, the orbit key the level kernel probes with.  (Init keeps its fingerprint
+// there too: it is its orbit's only member, and no action leads back to it.)  Roots equal by key count once.
+// Root k lives on the shard that owns its key, after the roots before it, with the parent record root_record(k).
+static int seed_level(rtla_ctx* x, const uint32_t* rows, size_t n, bool seeded, rtla_level_stats* st) {
+  const double t0 = now_s();
   HIPCHK(hipSetDevice(x->device));
   const Layout& L = x->L;
-  x->init_row.assign(L.W, 0);
-  row_init(L, x->init_row.data());
-  // Init belongs to the shard that owns its fingerprint (raft.tla:155-160: one state)
-  int owner = fp_owner(row_fp(x->init_row.data()), x->nshard);
-  for (auto& s : x->sh) {
+  const size_t W = (size_t)L.W;
+  std::vector<uint32_t> roots;
+  std::vector<FP> keys;
+  std::set<std::pair<uint64_t, uint64_t>> seen;
+  for (size_t k = 0; k < n; k++) {
+    std::vector<uint32_t> row(rows + k * W, rows + (k + 1) * W);
+    if (row_nmsg(L, row.data()) > L.K || row_nelec(L, row.data()) > L.E) return RTLA_E_ARG;  // no row of this layout
+    row_set_fp(row.data(), row_fingerprint(L, row.data()));
+    const FP key = seeded && L.sym
+                       ? dispatch_n(L, [&](auto ns) { return orbit_key_row<decltype(ns)::value>(L, row.data()); })
+                       : row_fp(row.data());
+    if (!seen.insert({key.a, key.b}).second) continue;
+    roots.insert(roots.end(), row.begin(), row.end());
+    keys.push_back(key);
+  }
+  const size_t nroot = keys.size();
+  // per local shard: its roots in the given order, and the same rows carrying their keys (what k_insert_rows reads)
+  struct Part {
+    std::vector<uint32_t> rows, keyed;
+    std::vector<uint64_t> recs;
+  };
+  std::vector<Part> part(x->sh.size());
+  std::vector<std::pair<int, uint64_t>> home(nroot, {-1, 0});  // root -> (local shard, its index there)
+  for (size_t k = 0; k < nroot; k++) {
+    const int owner = fp_owner(keys[k], x->nshard);
+    for (size_t q = 0; q < x->sh.size(); q++) {
+      if (x->sh[q].id != owner) continue;
+      Part& p = part[q];
+      home[k] = {(int)q, p.recs.size()};
+      p.rows.insert(p.rows.end(), roots.begin() + k * W, roots.begin() + (k + 1) * W);
+      p.keyed.insert(p.keyed.end(), roots.begin() + k * W, roots.begin() + (k + 1) * W);
+      row_set_fp(p.keyed.data() + p.keyed.size() - W, keys[k]);
+      p.recs.push_back(root_record(k));
+    }
+  }
+  uint64_t largest = 0;
+  for (size_t q = 0; q < x->sh.size(); q++) {
+    largest = std::max<uint64_t>(largest, part[q].recs.size());
+    if (part[q].recs.size() > std::min(x->front_cap, x->sh[q].parents_cap)) return RTLA_E_OVERFLOW;
+  }
+  for (size_t q = 0; q < x->sh.size(); q++) {
+    Shard& s = x->sh[q];
+    const Part& p = part[q];
+    const uint64_t m = p.recs.size();
     s.cur_start = 0; s.cur_base = 0; s.n_cur = 0;
-    if (s.id != owner) continue;
-    HIPCHK(hipMemcpyAsync(s.arena, x->init_row.data(), L.W * 4, hipMemcpyHostToDevice, x->stream));
-    HIPCHK(launch_insert_rows(L, s.arena, 1, s.table, x->tlog2, s.dflags, s.ctr, x->stream));
-    uint64_t root = ~0ull;
-    HIPCHK(hipMemcpyAsync(s.parents, &root, 8, hipMemcpyHostToDevice, x->stream));
-    s.n_cur = 1;
+    if (!m) continue;
+    HIPCHK(hipMemcpyAsync(s.arena, p.keyed.data(), m * W * 4, hipMemcpyHostToDevice, x->stream));
+    for (uint64_t b = 0; b < m; b += 64)  // (s.dflags holds 64 answers)
+      HIPCHK(launch_insert_rows(L, s.arena + b * W, std::min<uint64_t>(64, m - b), s.table, x->tlog2, s.dflags, s.ctr,
+                                x->stream));
+    if (seeded && L.sym) HIPCHK(hipMemcpyAsync(s.arena, p.rows.data(), m * W * 4, hipMemcpyHostToDevice, x->stream));
+    HIPCHK(hipMemcpyAsync(s.parents, p.recs.data(), m * 8, hipMemcpyHostToDevice, x->stream));
+    s.n_cur = m;
   }
   HIPCHK(hipStreamSynchronize(x->stream));
-  x->level = 1; x->distinct = 1; x->generated = 1; x->inited = true; x->max_front = 1;
-  int bad = check_invariants<0>(L, x->init_row.data(), (const Delta*)nullptr);
+  for (auto& s : x->sh) {  // (the next level's set-up clears the counters: a full set is reported here)
+    int flags = 0;
+    HIPCHK(hipMemcpy(&flags, &s.ctr->flags, sizeof flags, hipMemcpyDeviceToHost));
+    if (flags) {
+      report_flags(flags);
+      return flags_to_status(flags);
+    }
+  }
+  x->roots = std::move(roots);
+  x->seeded = seeded;
+  x->level = 1; x->distinct = nroot; x->generated = n; x->inited = true; x->max_front = largest;
   int status = RTLA_OK;
-  if (bad) {
-    if (Shard* s = x->local(owner)) { s->viol_mask = bad; s->viol_in_model = 1; s->viol_child = 0; s->viol_inst = -1; }
+  for (size_t k = 0; k < nroot && status == RTLA_OK; k++) {
+    const int bad = check_invariants<0>(L, x->roots.data() + k * W, (const Delta*)nullptr);
+    if (!bad) continue;
+    if (home[k].first >= 0) {
+      Shard& s = x->sh[(size_t)home[k].first];
+      s.viol_mask = bad; s.viol_in_model = 1; s.viol_child = home[k].second; s.viol_inst = -1;
+    }
     x->finished = true;
     status = RTLA_VIOLATION;
   }
   if (st) {
     memset(st, 0, sizeof *st);
-    st->level = 1; st->status = status; st->new_states = 1; st->generated = 1;
-    st->distinct_total = 1; st->generated_total = 1; st->seconds = now_s() - t0;
+    st->level = 1; st->status = status; st->new_states = nroot; st->generated = n;
+    st->distinct_total = nroot; st->generated_total = n; st->seconds = now_s() - t0;
     st->row_bytes = (uint64_t)L.W * 4;
   }
   return status;
+}
+
+extern "C" int rtla_init(rtla_ctx* x, rtla_level_stats* st) {
+  if (!x) return RTLA_E_ARG;
+  if (x->inited || x->cfg.mode == RTLA_MODE_DEDUP) return RTLA_E_STATE;
+  std::vector<uint32_t> init((size_t)x->L.W, 0);
+  row_init(x->L, init.data());  // (raft.tla:155-160: one state)
+  return seed_level(x, init.data(), 1, false, st);
+}
+
+extern "C" int rtla_init_rows(rtla_ctx* x, const uint32_t* rows, size_t n, rtla_level_stats* st) {
+  if (!x) return RTLA_E_ARG;
+  if (x->inited || x->cfg.mode == RTLA_MODE_DEDUP || x->world > 1) return RTLA_E_STATE;
+  if (!rows || n == 0) return RTLA_E_ARG;
+  return seed_level(x, rows, n, true, st);
 }
 
 // ---- multi-shard exchange (the transport -- device copies for local shards,
@@ -1126,7 +1201,7 @@ static int trace_start(rtla_ctx* x, bool bad, uint64_t start[4]) {
   } else if (vs) {
     start[0] = 1;
     start[1] = (uint64_t)vs->id;
-    if (vs->viol_inst < 0) { start[2] = 0; start[3] = 0; }
+    if (vs->viol_inst < 0) { start[2] = vs->viol_child; start[3] = 0; }  // a violating root (Init: index 0)
     else if (vs->viol_in_model && vs->viol_child != ~0ull) { start[2] = vs->viol_child; start[3] = 0; }
     else { start[2] = vs->viol_parent; start[3] = (uint64_t)vs->viol_inst + 1; }
   }
@@ -1147,10 +1222,10 @@ static int trace_start(rtla_ctx* x, bool bad, uint64_t start[4]) {
 }
 
 // Counterexample: find where it starts (trace_start), walk the parent records
-// back to Init -- across shards: a record names its parent's shard
-// (parent_record, rtla_device.h) -- then replay the action instances forward from the Init row with
-// the kernel that built them.  Collective when world > 1 (every rank calls it;
-// each step's record comes from the rank that holds it).
+// back to a root (Init, or the row of a seeded search the record names: root_record, rtla_ctx.h) -- across
+// shards: a record names its parent's shard (parent_record, rtla_device.h) -- then replay the action
+// instances forward from that root's row with the kernel that built them.  Collective when world > 1
+// (every rank calls it; each step's record comes from the rank that holds it).
 extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t cap, size_t* n_rows) {
   if (!x || !n_rows) return RTLA_E_ARG;
   // world > 1: every rank reaches every reduction below; a local failure
@@ -1163,22 +1238,26 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
   if (int rc = trace_start(x, bad, start)) return rc;
   std::vector<int32_t> insts;
   if (start[3]) insts.push_back((int32_t)(start[3] - 1));
-  uint64_t shard = start[1], g = start[2];
+  uint64_t shard = start[1], g = start[2], root = ~0ull;
   for (int guard = 0; guard < (1 << 20); guard++) {
     uint64_t p = 0;
     if (int rc = comm_parent_record(x, shard, g, bad, &p)) return rc;
-    if (p == ~0ull) break;  // Init
+    if (is_root_record(p)) {  // Init, or root k of a seeded search
+      root = root_of(p);
+      break;
+    }
     insts.push_back(parent_inst(p));
     shard = parent_shard(p);
     g = parent_index(p);
   }
+  if (root >= x->roots.size() / (size_t)L.W) return RTLA_E_STATE;  // (the walk met no root record of this search)
   std::reverse(insts.begin(), insts.end());
   // a simulated violation: the walk's states after the BFS chain, the violating successor last
   size_t n = insts.size() + 1 + (simv ? (size_t)x->sim.step : 0);
   *n_rows = n;
   if (!rows && !labels) return RTLA_OK;
   if (n > cap) return RTLA_E_ARG;
-  std::vector<uint32_t> row = x->init_row;
+  std::vector<uint32_t> row(x->roots.begin() + root * L.W, x->roots.begin() + (root + 1) * L.W);
   uint32_t* d_row = nullptr;
   HIPCHK(hipMalloc(&d_row, 64 * L.W * 4));  // a whole 64-row group (the level kernel's tile)
   if (rows) memcpy(rows, row.data(), L.W * 4);

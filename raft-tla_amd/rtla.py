@@ -89,6 +89,7 @@ def _load():
         "rtla_open": (C.c_int, [P(_Cfg), C.c_int, C.c_int, C.c_void_p, P(C.c_void_p)]),
         "rtla_close": (None, [C.c_void_p]),
         "rtla_init": (C.c_int, [C.c_void_p, P(_Stats)]),
+        "rtla_init_rows": (C.c_int, [C.c_void_p, P(C.c_uint32), C.c_size_t, P(_Stats)]),
         "rtla_step": (C.c_int, [C.c_void_p, P(_Stats)]),
         "rtla_reset": (C.c_int, [C.c_void_p]),
         "rtla_violation": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32)]),
@@ -180,7 +181,7 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_check_replay", "rtla_check_frontier", "rtla_fpset_probe", "rtla_pred_compile", "rtla_pred_free",
             "rtla_pred_count", "rtla_pred_name", "rtla_pred_replay", "rtla_pred_batch", "rtla_pred_frontier",
             "rtla_pred_compile_step", "rtla_pred_is_step", "rtla_pred_step_replay", "rtla_pred_step_batch",
-            "rtla_pred_step_frontier"]
+            "rtla_pred_step_frontier", "rtla_init_rows"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -713,9 +714,17 @@ class Checker:
                                  st.kernel_ms, st.probes, st.row_bytes, st.expand_ms))
         self.distinct, self.generated = st.distinct_total, st.generated_total
 
-    def init(self) -> int:
+    def init(self, roots=None) -> int:
+        """Level 1: Init -- or, roots given (a list of rows, or rows already
+        flat), those rows (rtla_init_rows: TLC's INIT override for explicit
+        states).  Equal roots count once; a root that violates an invariant
+        gives VIOLATION and a one-row trace; such a search has no checkpoint."""
         st = _Stats()
-        self.status = _check(_lib.rtla_init(self._h, C.byref(st)), "rtla_init")
+        if roots is None:
+            self.status = _check(_lib.rtla_init(self._h, C.byref(st)), "rtla_init")
+        else:
+            flat, n = _flat_rows(roots, row_words(self.cfg))
+            self.status = _check(_lib.rtla_init_rows(self._h, flat, n, C.byref(st)), "rtla_init_rows")
         self._rec(st)
         return self.status
 
@@ -739,8 +748,9 @@ class Checker:
         return self.status
 
     def run(self, max_levels: int = 100000, predicates: Optional[Predicates] = None,
-            actions: Optional[Predicates] = None) -> int:
-        """BFS until the search ends, a violation or max_levels.  predicates: a
+            actions: Optional[Predicates] = None, roots=None) -> int:
+        """BFS until the search ends, a violation or max_levels.  roots: the
+        rows level 1 holds instead of Init (init(roots)).  predicates: a
         set audited on every level right after it is produced, Init's included
         (audit_predicates); the run stops with VIOLATION at the first level that
         holds a state on which a definition is false.  actions: a step set
@@ -756,7 +766,7 @@ class Checker:
             return self.status
 
         if not self.levels and not self._recovered:
-            if self.init() != OK or audited() != OK:
+            if self.init(roots) != OK or audited() != OK:
                 return self.status
         while self.status == OK and len(self.levels) < max_levels:
             self.step()
@@ -946,13 +956,14 @@ class Checker:
 
 
 def check(cfg: Config, trace: bool = True, predicates: Optional[Predicates] = None,
-          actions: Optional[Predicates] = None) -> Result:
-    """Exhaustive BFS of the model (TLC `-workers N` breadth-first mode).
+          actions: Optional[Predicates] = None, roots=None) -> Result:
+    """Exhaustive BFS of the model (TLC `-workers N` breadth-first mode), from
+    Init or from the rows `roots` (Checker.init).
     predicates: user-defined invariants checked on every level (Checker.run);
     actions: action properties checked on the steps out of every level;
     Result.violation then names the false definitions."""
     with Checker(cfg) as ck:
-        st = ck.run(predicates=predicates, actions=actions)
+        st = ck.run(predicates=predicates, actions=actions, roots=roots)
         res = Result(distinct=ck.distinct, generated=ck.generated, levels=list(ck.levels))
         res.depth = sum(1 for lv in ck.levels if lv.new > 0)
         res.seconds = sum(lv.seconds for lv in ck.levels)
