@@ -118,6 +118,13 @@ enum {
                               // (rtla_expand_batch: the parity seam runs the hot kernel)
 };
 
+// Phase slots of the level kernel's cycle stamps: the diagnostic build (RTLA_STAMPS, every unit compiled
+// with it) splits the group start into tile load and per-state setup and so has one more.
+#ifdef RTLA_STAMPS
+#define RTLA_NSTAMP 9
+#else
+#define RTLA_NSTAMP 8
+#endif
 // Per-level device counters (zeroed before each level except `cover`).
 struct DevCounters {
   unsigned long long generated;
@@ -131,7 +138,7 @@ struct DevCounters {
   unsigned long long viol_child;
   unsigned long long group_next;  // k_expand_compact's work queue (zeroed before each launch)
   unsigned long long group_size;  // frontier states per group of the last k_expand_compact launch
-  unsigned long long stamp[8];    // RTLA_STAMPS builds: cycles per level-kernel phase, summed over waves
+  unsigned long long stamp[RTLA_NSTAMP];  // RTLA_STAMPS builds: cycles per level-kernel phase, summed over waves
   unsigned long long cas;         // RTLA_COUNT_CAS builds: pipelined fingerprint-set CAS issued by the level kernel
   unsigned long long exp[SHARD_MAX];  // multi-shard: export slots reserved for owner p (re-homed at level end) ...
   unsigned long long exp_cut[SHARD_MAX];  // ... and 1 + the first slot of the batch that did not fit (0: none)

@@ -719,13 +719,14 @@ void print_stamps(const DevCounters& c, int level) {
   if (!getenv("RTLA_STAMPS_PRINT")) return;
   if (c.cas) fprintf(stderr, "cas level %d: %llu pipelined CAS, %llu probes, %llu new\n", level,
                      (unsigned long long)c.cas, (unsigned long long)c.probes, (unsigned long long)c.next_count);
-  static const char* ph[8] = {"group", "ring", "compute", "resolve", "issue", "rows", "drain", "keys+end"};
-  // (non-symmetric kernels: "drain" = the group-end row build, "keys+end" = the group-end probe drain)
+  static const char* ph[9] = {"setup", "ring", "compute", "resolve", "issue", "rows", "drain", "keys+end", "tile"};
+  // (the group start is "tile", the row tile load, then "setup", the per-state setup; non-symmetric kernels:
+  // "drain" = the group-end row build, "keys+end" = the group-end probe drain)
   unsigned long long tot = 0;
-  for (int k = 0; k < 8; k++) tot += c.stamp[k];
+  for (int k = 0; k < RTLA_NSTAMP; k++) tot += c.stamp[k];
   if (!tot) return;
   fprintf(stderr, "stamps level %d:", level);
-  for (int k = 0; k < 8; k++) fprintf(stderr, " %s %.3f", ph[k], (double)c.stamp[k] / tot);
+  for (int k = 0; k < RTLA_NSTAMP; k++) fprintf(stderr, " %s %.3f", ph[k], (double)c.stamp[k] / tot);
   fprintf(stderr, " (%.3g wave-cycles)\n", (double)tot);
 }
 

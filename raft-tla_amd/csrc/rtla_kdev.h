@@ -89,9 +89,12 @@ __device__ __forceinline__ WaveLds wave_lds(uint32_t* lds, int wave, int W) {
   return WaveLds{prow, pall, reinterpret_cast<FP*>(pall + 32), pall + 32 + 4 * NMAX};
 }
 
-// Copy n contiguous words global -> LDS (dst and src 16-byte aligned) with 8
-// 16-byte loads in flight per lane (a plain loop waits for every load before
-// its LDS store).
+// Copy n contiguous words global -> LDS (dst and src 16-byte aligned) through
+// registers, 16 bytes per lane and step, written as 8 loads per lane before
+// their 8 LDS stores.  Inside a kernel short of registers the compiler does
+// not keep that order: in the level kernels (at their VGPR cap, spilling) it
+// staged every load in the same four VGPRs, one load, one wait, one LDS write
+// at a time -- which is why their tile load is copy_words_lds_dma below.
 __device__ __forceinline__ void copy_words_lds16(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int n,
                                                  int lane) {
   const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
@@ -108,6 +111,28 @@ __device__ __forceinline__ void copy_words_lds16(uint32_t* __restrict__ dst, con
   for (; w < n4; w += 64) d4[w] = s4[w];
   for (int t = (n4 << 2) + lane; t < n; t += 64) dst[t] = src[t];
 }
+
+// The same copy by LDS-DMA (global_load_lds: memory -> LDS, no destination
+// registers, so every piece is in flight at once whatever the kernel's
+// register pressure): one 16-byte piece per lane and step -- a step writes
+// LDS at its wave-uniform base + lane * 16, only the lanes that still have a
+// piece take part -- then the last n % 4 words with the 4-byte form (base +
+// lane * 4).  Exactly n words are written.  NOTHING orders these writes
+// against the wave's LDS accesses but the caller:
+//   before: s_waitcnt lgkmcnt(0) if earlier LDS reads of dst may be in flight
+//           (a DMA write is not queued behind them);
+//   after:  s_waitcnt vmcnt(0) (dma_wait) before the first read of dst.
+__device__ __forceinline__ void copy_words_lds_dma(uint32_t* dst, const uint32_t* src, int n, int lane) {
+  using GPtr = const __attribute__((address_space(1))) void*;
+  using LPtr = __attribute__((address_space(3))) void*;
+  const int n4 = n >> 2;
+  for (int p = 0; p < n4; p += 64)
+    if (p + lane < n4) __builtin_amdgcn_global_load_lds((GPtr)(src + 4 * (p + lane)), (LPtr)(dst + 4 * p), 16, 0, 0);
+  const int t = n4 << 2;
+  if (t + lane < n) __builtin_amdgcn_global_load_lds((GPtr)(src + t + lane), (LPtr)(dst + t), 4, 0, 0);
+}
+__device__ __forceinline__ void lds_reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Gather nv rows of W words (row r from src_row(r), a wave-uniform address)
 // into LDS rows dst + r * W: lane l moves words l, l + 64, ... of each row,

@@ -308,7 +308,7 @@ __device__ __noinline__ BuildOut build_one(const Layout& Lrt, const uint32_t* pr
 #ifdef RTLA_STAMPS
 #define RTLA_STAMP_DECL                                                   \
   unsigned long long st_prev_ = __builtin_amdgcn_s_memtime();              \
-  unsigned long long st_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st_acc_[RTLA_NSTAMP] = {};
 #define STAMP(k)                                                             \
   do {                                                                       \
     const unsigned long long t_ = __builtin_amdgcn_s_memtime();              \
@@ -317,7 +317,7 @@ __device__ __noinline__ BuildOut build_one(const Layout& Lrt, const uint32_t* pr
   } while (0)
 #define RTLA_STAMP_FLUSH(ctr, lane)                                          \
   if ((lane) == 0)                                                           \
-    for (int k_ = 0; k_ < 8; k_++) atomicAdd(&(ctr)->stamp[k_], st_acc_[k_]);
+    for (int k_ = 0; k_ < RTLA_NSTAMP; k_++) atomicAdd(&(ctr)->stamp[k_], st_acc_[k_]);
 #else
 #define RTLA_STAMP_DECL
 #define STAMP(k)
@@ -918,11 +918,21 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       const uint32_t* src = ring_row(cur, s0, W);
       const int nw = nvalid * W;
       // 16-byte aligned: s0 * W * 4 is a multiple of 128 * W, and the row tile's LDS offset of 16
-      if (RTLA_IDX_OK(ctr, ring_idx(cur, s0) + nvalid, cur.cap + 1)) copy_words_lds16(rows, src, nw, lane);
+      // By LDS-DMA: every piece of the tile is requested before the wave waits for any, with no staging
+      // registers (a register-staged copy came out as one load, one wait, one LDS write at a time in
+      // these kernels: rtla_kdev.h).  The previous group's row build may still have LDS reads of the
+      // tile in flight, and a DMA write is not ordered behind them: they are waited for first (the
+      // build has consumed them all by now).  The tile is read only after the DMA's own wait.
+      // (Every instantiation: configs[1] 150.7-153.3 -> 140.6-142.5 ms, the narrow-row exhaust model
+      // 1123-1125 -> 1101-1103 ms; profiles/r12_tile/tile_ab.txt)
+      lds_reads_done();
+      if (RTLA_IDX_OK(ctr, ring_idx(cur, s0) + nvalid, cur.cap + 1)) copy_words_lds_dma(rows, src, nw, lane);
+      dma_wait();
     }
     if constexpr (!narrow)  // (the previous group end's line touches: returned before this tile did)
       asm volatile("" ::"v"(pfa_c), "v"(pfb_c));
     wave_sync();
+    STAMP(8);  // row tile load (and the wait for the work-queue atomic issued before it)
     // the next group's number (its atomic returned before the tile copy's wait; MULTI: taken at the group's end)
     unsigned long long gnn = MULTI ? 0ull : shfl0_u64(gnext);
     const bool valid = lane < nvalid;
@@ -945,7 +955,7 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
       }
     }
     wave_sync();
-    STAMP(0);  // group start: work-queue atomic, row tile load, per-state setup
+    STAMP(0);  // per-state setup
     // With at most one copy of a message allowed (max copies 1), every
     // DuplicateMessage successor (raft.tla:443-445) is out of the model: its
     // one message's count becomes 2 (specs/MC.tla).  It differs from its
@@ -1062,8 +1072,10 @@ k_expand_compact(Layout Lrt, Ring cur, unsigned long long s_begin, unsigned long
     // touches above would drain them all): the next group's tile load is
     // issued behind them, and its own wait -- which it needs anyway -- is the
     // first to cover them.  The tile may be overwritten: the row build read
-    // it from LDS into registers before storing, and LDS operations of a
-    // wave complete in order.  (The narrow-row kernels keep the wait and
+    // it from LDS into registers before storing; a register-staged tile copy
+    // writes LDS behind those reads (LDS operations of a wave complete in
+    // order), the LDS-DMA one waits for them itself (lds_reads_done at the
+    // head of the loop).  (The narrow-row kernels keep the wait and
     // consume the touches here: carried over the loop they cost the
     // 128-VGPR kernel 20-90 ms per exhaust-model run.)
     if constexpr (narrow) {

@@ -10,8 +10,8 @@ D=$ROOT/exp/$name; rm -rf $D; mkdir -p $D
 H=/opt/rocm/bin/hipcc
 F="-O3 -std=c++20 -fPIC --offload-arch=gfx950 -Wno-unused-result $*"
 S=${SRC:-$ROOT/raft-tla_amd/csrc}  # SRC: a modified copy of csrc/ (its ../../include must hold rtla.h)
-ALL=${ALL_UNITS:-"rtla_kernels rtla_kwave rtla_kpack rtla_kspec_a rtla_kspec_b rtla_ksym_a rtla_ksym_b rtla_kgeneric_a rtla_kgeneric_b rtla_ksim rtla_kaudit"}  # the kernel units (raft-tla_amd/Makefile KUNITS)
-HOST="rtla_host rtla_comm rtla_ckpt rtla_simhost rtla_audit rtla_rows rtla_text"  # the host units (raft-tla_amd/Makefile HUNITS)
+ALL=${ALL_UNITS:-"rtla_kernels rtla_kwave rtla_kpack rtla_kspec_a rtla_kspec_b rtla_ksym_a rtla_ksym_b rtla_kgeneric_a rtla_kgeneric_b rtla_ksim rtla_kaudit rtla_kpred"}  # the kernel units (raft-tla_amd/Makefile KUNITS)
+HOST="rtla_host rtla_comm rtla_ckpt rtla_simhost rtla_audit rtla_rows rtla_text rtla_pred rtla_predhost"  # the host units (raft-tla_amd/Makefile HUNITS)
 pids=""
 if [ -n "$UNITS" ]; then
   for u in $ALL $HOST; do cp $ROOT/raft-tla_amd/build/$u.o $D/$u.o; done
