@@ -53,6 +53,10 @@
  *   rtla_pred_step_frontier ... an action property `Name == [][A]_vars` named
  *                            under PROPERTY: the same bytecode over a step's two
  *                            states, checked on every step out of a BFS level.
+ *   rtla_simulate_pred       -simulate with operators of MC.tla named under
+ *                            INVARIANT / PROPERTY: the walks carry a compiled
+ *                            state set and / or action set (rtla_sim_replay_pred,
+ *                            rtla_sim_walk_pred: the same on the host).
  *   rtla_sim_replay,
  *   rtla_sim_walk            the same walks recomputed on the host from
  *                            (seed, walk id): reproduce one behaviour, as TLC
@@ -308,6 +312,44 @@ int rtla_sim_replay(const rtla_cfg *cfg, const uint32_t *start_rows, size_t n_st
  * set even if cap is too small (RTLA_E_ARG). */
 int rtla_sim_walk(const rtla_cfg *cfg, const uint32_t *start_row, uint64_t seed, uint64_t walk, int32_t depth,
                   uint32_t *rows, int32_t *labels, size_t cap, size_t *n_rows);
+
+/* The same walks carrying user properties (normative
+ * text: raft-tla_amd/csrc/rtla_sim.h): a compiled state set `states`
+ * (rtla_pred_compile) and / or a compiled action set `steps`
+ * (rtla_pred_compile_step).  Either may be NULL; both NULL, a set of the wrong
+ * kind or one compiled for another row layout: RTLA_E_ARG.  At every step the
+ * action set is evaluated on (state, successor) for every enabled successor,
+ * as rtla_pred_step_* does (a stuttering step satisfies every definition), the
+ * state set on every in-model successor; the walk ends at the least instance
+ * whose built-in mask, state mask or step mask is nonzero.  A set never changes
+ * which walk is taken.  An evaluation error of either program fails the call
+ * (RTLA_E_SPEC).  The start row itself is not evaluated.
+ * ends5 (may be NULL; 5 * n_walks u64): words 0-3 as rtla_simulate's; word 4 is
+ * 0 unless the walk stopped on a violation, then instance | in_model << 16 |
+ * built-in mask << 24 | state mask << 32 | step mask << 40.
+ * out->viol_mask keeps meaning the built-in bits; pout names the rest.  After
+ * RTLA_VIOLATION from rtla_simulate_pred, rtla_trace replays the walk with the
+ * sets (they need not outlive the call) and rtla_violation returns the built-in
+ * mask if nonzero, else the state mask, else the step mask. */
+typedef struct {
+    uint64_t state_evaluated; /* evaluations of the state set (in-model successors) */
+    uint64_t step_evaluated;  /* evaluations of the action set (== generated when given) */
+    int32_t viol_inv_mask;    /* the reported successor's violated RTLA_INV_*, ... */
+    int32_t viol_state_mask;  /* ... its false state definitions (bit k = definition k) and ... */
+    int32_t viol_step_mask;   /* ... its false action definitions */
+    int32_t reserved;
+} rtla_sim_pred_stats;
+struct rtla_pred; /* a compiled set: rtla_pred_compile / rtla_pred_compile_step, below */
+int rtla_simulate_pred(rtla_ctx *ctx, uint64_t seed, uint64_t first_walk, uint64_t n_walks, int32_t depth,
+                       const struct rtla_pred *states, const struct rtla_pred *steps, uint64_t *ends5,
+                       rtla_sim_stats *out, rtla_sim_pred_stats *pout);
+int rtla_sim_replay_pred(const rtla_cfg *cfg, const uint32_t *start_rows, size_t n_start, uint64_t seed,
+                         uint64_t first_walk, uint64_t n_walks, int32_t depth, int threads,
+                         const struct rtla_pred *states, const struct rtla_pred *steps, uint64_t *ends5,
+                         rtla_sim_stats *out, rtla_sim_pred_stats *pout);
+int rtla_sim_walk_pred(const rtla_cfg *cfg, const uint32_t *start_row, uint64_t seed, uint64_t walk, int32_t depth,
+                       const struct rtla_pred *states, const struct rtla_pred *steps, uint32_t *rows,
+                       int32_t *labels, size_t cap, size_t *n_rows);
 
 /* Audit: invariants evaluated outside the search.  inv_mask (RTLA_INV_*) is the
  * set to evaluate, independent of cfg->inv_mask and of a context's own set.

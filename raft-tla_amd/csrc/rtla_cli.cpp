@@ -24,6 +24,7 @@
 // A name under PROPERTY / PROPERTIES is accepted when it is an action definition
 // `Name == [][A]_vars` of FILE: it is checked on every
 // step out of every level; -audit may name one too (the steps out of the last level).
+// With -simulate the same sets go into the walks.
 //
 // SPEC.tla is either the reference's raft.tla (sha256 checked: the semantics
 // are compiled into the kernels, not parsed) or a wrapper module that
@@ -231,7 +232,9 @@ void usage() {
           "            -config FILE.cfg SPEC.tla\n"
           "  -simulate: after K BFS levels (default 1 = Init only) run N random walks (default 1000000) of up to\n"
           "  D steps (default 100) from the states of level K; walk ids F .. F+N-1 are global, so runs with\n"
-          "  disjoint ranges and the same seed compose; one GPU only.\n"
+          "  disjoint ranges and the same seed compose; one GPU only.  With -predicates FILE the cfg's user\n"
+          "  INVARIANT and PROPERTY names are checked in the walks too: the action properties on every step out of\n"
+          "  every state a walk visits, the invariants on every in-model successor.\n"
           "  -predicates FILE: definitions in the predicate language (specs/MCPredicates.tla) that INVARIANT(S) and\n"
           "          -audit may name beside the built-in invariants; checked on every level of the search (-gpus 1).\n"
           "          Its action definitions `Name == [][A]_vars` (specs/MCActions.tla) may be named under\n"
@@ -922,7 +925,9 @@ int main(int argc, char** argv) {
   }
   // -simulate: the BFS stopped at level K with nothing found (a BFS that
   // finished or violated first is reported below as without -simulate)
-  bool simulated = false;
+  bool simulated = false, sim_with_sets = false;
+  rtla_sim_pred_stats sps;  // the walks' violation when they carried the user's sets: three masks
+  memset(&sps, 0, sizeof sps);
   if (simulate && st == RTLA_OK) {
     simulated = true;
     size_t nfront = 0;
@@ -933,7 +938,20 @@ int main(int argc, char** argv) {
            (unsigned long long)sim_first, (unsigned long long)(sim_first + sim_num - (sim_num ? 1 : 0)));
     rtla_sim_stats ss;
     memset(&ss, 0, sizeof ss);
-    st = rtla_simulate(ctx, sim_seed, sim_first, sim_num, sim_depth, nullptr, &ss);
+    if (preds || actions) {  // the cfg's user INVARIANTs and PROPERTYs go into the walks: the sets check_level audits
+      std::string line = "Checking in the walks:";
+      const rtla_pred* sets[2] = {preds, actions};
+      for (int q = 0; q < 2; q++) {
+        if (!sets[q]) continue;
+        line += q == 0 ? " invariants " : preds ? "; action properties " : " action properties ";
+        for (int k = 0; k < rtla_pred_count(sets[q]); k++) line += (k ? ", " : "") + pred_name(sets[q], k);
+      }
+      printf("%s.\n", line.c_str());
+      sim_with_sets = true;
+      st = rtla_simulate_pred(ctx, sim_seed, sim_first, sim_num, sim_depth, preds, actions, nullptr, &ss, &sps);
+    } else {
+      st = rtla_simulate(ctx, sim_seed, sim_first, sim_num, sim_depth, nullptr, &ss);
+    }
     if (st < 0) {
       printf("Error: %s\n", rtla_strerror(st));
       rtla_close(ctx);
@@ -957,7 +975,15 @@ int main(int argc, char** argv) {
   if (st == RTLA_VIOLATION) {
     int32_t mask = 0, inm = 0;
     rtla_violation(ctx, &mask, &inm);
-    if (pred_violation) {
+    if (simulated && sim_with_sets) {  // every false thing of the reported successor: built-ins first
+      for (auto& i : INVARIANTS)
+        if (sps.viol_inv_mask & i.bit) printf("Error: Invariant %s is violated.\n", i.name);
+      for (int k = 0; preds && k < rtla_pred_count(preds); k++)
+        if (sps.viol_state_mask >> k & 1) printf("Error: Invariant %s is violated.\n", pred_name(preds, k).c_str());
+      for (int k = 0; actions && k < rtla_pred_count(actions); k++)
+        if (sps.viol_step_mask >> k & 1)
+          printf("Error: Action property %s is violated.\n", pred_name(actions, k).c_str());
+    } else if (pred_violation) {
       for (int k = 0; k < rtla_pred_count(viol_set); k++)  // every false definition of the state, in file order
         if (mask >> k & 1)
           printf("Error: %s %s is violated.\n", rtla_pred_is_step(viol_set) ? "Action property" : "Invariant",

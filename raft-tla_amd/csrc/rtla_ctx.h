@@ -73,13 +73,15 @@ struct Shard {
 // and the violation its last call found (rtla_violation / rtla_trace).
 struct SimState {
   SimCounters* ctr = nullptr;
-  uint64_t* ends = nullptr;    // [ends_cap][4] end records of the batch
+  uint64_t* ends = nullptr;    // [ends_cap] u64: the batch's end records (4 words each; 5 with user properties)
+  uint32_t* prog = nullptr;    // rtla_simulate_pred: the device copy of both programs (2 * PRED_MAX_WORDS words)
   uint32_t* carry = nullptr;   // [carry_cap][W] current rows of a batch whose depth is split across launches
   uint64_t ends_cap = 0, carry_cap = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool viol = false;
   uint64_t seed = 0, walk = 0, start = 0;  // start: parent-record index of the walk's start row
   int step = 0, inst = -1, mask = 0, in_model = 0;
+  std::vector<uint32_t> scode, acode;  // rtla_simulate_pred: the programs the violating walk is replayed with
 };
 
 // rtla_check_frontier's device counters and events (allocated at first use)
@@ -270,9 +272,10 @@ int replay_rows(size_t n, int threads, int32_t* masks, uint64_t* counts, uint64_
 uint64_t rows_digest(const Layout& L, const uint32_t* rows, size_t n, int threads, bool orbit = false);
 int expand_batch_dev(const Layout& L, const uint32_t* d_rows, size_t n, std::vector<uint32_t>& out,
                      std::vector<uint64_t>& info, hipStream_t st);
-// rtla_simhost.cpp: one walk's states (and, last, its violating successor) from the host
+// rtla_simhost.cpp: one walk's states (and, last, its violating successor) from the host; sprog / aprog: the
+// programs of the state set and the action set the walk carries, or null
 int sim_walk_rows(const Layout& L, const uint32_t* start, uint64_t seed, uint64_t walk, int depth, uint32_t* rows,
-                  int32_t* labels, size_t cap, size_t* n_rows);
+                  int32_t* labels, size_t cap, size_t* n_rows, const uint32_t* sprog, const uint32_t* aprog);
 
 // ---- rtla_comm.cpp: collectives between ranks.  Every function is called
 // by every rank in the same order; device buffers, in stream order.

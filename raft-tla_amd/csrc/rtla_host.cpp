@@ -144,7 +144,7 @@ extern "C" void rtla_close(rtla_ctx* x) {
   (void)hipSetDevice(x->device);
   for (auto& s : x->sh) free_shard(s);
   if (x->red) (void)hipFree(x->red);
-  for (void* p : {(void*)x->sim.ctr, (void*)x->sim.ends, (void*)x->sim.carry})
+  for (void* p : {(void*)x->sim.ctr, (void*)x->sim.ends, (void*)x->sim.carry, (void*)x->sim.prog})
     if (p) (void)hipFree(p);
   if (x->sim.ev0) (void)hipEventDestroy(x->sim.ev0);
   if (x->sim.ev1) (void)hipEventDestroy(x->sim.ev1);
@@ -1283,7 +1283,9 @@ extern "C" int rtla_trace(rtla_ctx* x, uint32_t* rows, int32_t* labels, size_t c
     const size_t at = insts.size() + 1;
     size_t got = 0;
     rc = sim_walk_rows(L, row.data(), x->sim.seed, x->sim.walk, x->sim.step, rows ? rows + at * L.W : nullptr,
-                       labels ? labels + at : nullptr, n - at, &got);
+                       labels ? labels + at : nullptr, n - at, &got,
+                       x->sim.scode.empty() ? nullptr : x->sim.scode.data(),
+                       x->sim.acode.empty() ? nullptr : x->sim.acode.data());
     if (rc == RTLA_VIOLATION && got == (size_t)x->sim.step) rc = RTLA_OK;
     else if (rc >= 0) rc = RTLA_E_STATE;
   }

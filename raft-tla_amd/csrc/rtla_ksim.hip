@@ -12,6 +12,18 @@
 //     it (child_patches, incremental fingerprint: as materialize does);
 //   * global traffic: the start row, the end record, the counters -- and the
 //     current row of a walk whose depth is split across launches.
+//
+// k_simulate<NS, true> (k_simulate_pred) is the same walk carrying user
+// properties (rtla_sim.h).  The interpreter reads rows, so inside
+// the chunk loop the enabled lanes, ranked by ballot, materialise their child
+// (parent + patches) into a per-wave LDS stage, `tc` at a time, as k_pred_step
+// does, and the lane whose child is in the stage runs the action program on
+// (current row, child) and, if the child is in-model, the state program on the
+// child; the child never leaves the CU.  Per wave, after the plain kernel's
+// words: tc children at the odd stride W | 1, then tc operand files at
+// PRED_STRIDE; both programs are copied once per block into LDS.  Everything
+// this adds is under `if constexpr (PRED)`, and the last kernel argument of
+// k_simulate<NS, false> is an empty struct: the plain kernel is the code it was.
 #include "rtla_kdev.h"
 #include "rtla_sim.h"
 
@@ -28,29 +40,84 @@ __host__ __device__ constexpr int sim_wave_words(int W) { return (2 * even_words
 // 215 VGPRs at 128 and were not measured: they stay at 3 (17 / 30 spilled).
 constexpr int sim_waves(int ns) { return ns <= 3 ? 4 : 3; }
 
+// ---- walks with user properties
+constexpr int PRED_STRIDE = PRED_FILE + 1;  // words between two operand files: odd (rtla_kpred.hip)
+constexpr int SIM_WPB = 4;
+static_assert(PRED_STRIDE % 2 == 1, "conflict-free operand files need an odd stride");
+// Waves per SIMD of k_simulate_pred's register budget: the interpreter's state is live across the walk's, so it
+// has a budget of its own.  On the configs[1] shape 2 / 3 waves per SIMD (256 / 168 VGPRs, 28 / 333 spilled) ran
+// 2^21 walks x 32 steps with LeaderAppendOnly in 1,275 / 1,800 ms (profiles/r11_simpred).
+#ifndef SIM_PRED_WAVES
+#define SIM_PRED_WAVES 2
+#endif
+constexpr int sim_pred_waves(int) { return SIM_PRED_WAVES; }
+__host__ __device__ constexpr int sim_child_stride(int W) { return W | 1; }
+__host__ __device__ constexpr int sim_pred_wave_words(int W, int tc) {
+  return (sim_wave_words(W) + tc * (sim_child_stride(W) + PRED_STRIDE) + 3) & ~3;
+}
+// A block's LDS: the coverage tally, both programs, four waves.
+__host__ __device__ constexpr int sim_pred_block_bytes(int W, int tc) {
+  return (COVER_CODES + 2 * PRED_MAX_WORDS + SIM_WPB * sim_pred_wave_words(W, tc)) * 4;
+}
+// Children per tile: the most (at most 64) a block's LDS allows -- 64 KB, and no more than a CU's 160 KB divided by
+// the blocks of four waves its register budget lets it hold (one per wave per SIMD), so LDS never lowers them.
+__host__ __device__ constexpr int sim_tile_children(int W) {
+  const int per_cu = 160 * 1024 / SIM_PRED_WAVES;
+  const int budget = (per_cu < 65536 ? per_cu : 65536) / 4 - COVER_CODES - 2 * PRED_MAX_WORDS;
+  const int tc = (budget / SIM_WPB - sim_pred_wave_words(W, 0) - 3) / (sim_child_stride(W) + PRED_STRIDE);
+  return tc > 64 ? 64 : tc;
+}
+static_assert(sim_tile_children(WMAX) >= 4 && sim_tile_children(43) >= 4, "the widest row's tile holds a few children");
+static_assert(sim_pred_block_bytes(WMAX, sim_tile_children(WMAX)) <= 65536 &&
+                  sim_pred_block_bytes(43, sim_tile_children(43)) <= 65536 &&
+                  sim_pred_block_bytes(WMAX, sim_tile_children(WMAX)) * SIM_PRED_WAVES <= 160 * 1024 &&
+                  sim_pred_block_bytes(43, sim_tile_children(43)) * SIM_PRED_WAVES <= 160 * 1024,
+              "a block's LDS, and every block the registers allow on a CU");
+
+// What k_simulate_pred has beside k_simulate's arguments.
+struct SimNoArgs {};
+struct SimPredArgs {
+  const uint32_t* prog;  // the state program, and at PRED_MAX_WORDS the action program
+  int n_state, n_step;   // their words (0: no such set)
+  int tc;                // children per tile
+};
+
 }  // namespace
 
 // Walks [0, n_walks) of the batch whose first global walk id is `first`, steps
 // t0 + 1 .. t1 of `depth`.  t0 == 0: the walk starts at frontier row
 // (first + i) mod n_front; otherwise at carry[i] if ends[4 i + 3] says the walk
 // is still running (t0 steps taken, stop code 0).
-template <int NS>
+//
+// PRED (k_simulate_pred below): the walks carry user properties (pa: SimPredArgs, else an empty SimNoArgs); the end
+// records have 5 words, and word 4 of a walk that ended in an earlier launch is left alone (as its other words).
+template <int NS, bool PRED = false>
 __global__ void __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(sim_waves(NS))))
+__attribute__((amdgpu_waves_per_eu(PRED ? sim_pred_waves(NS) : sim_waves(NS))))
 k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long seed, unsigned long long first,
            unsigned int n_walks, int t0, int t1, int depth, uint32_t* __restrict__ carry,
-           unsigned long long* __restrict__ ends, SimCounters* ctr) {
+           unsigned long long* __restrict__ ends, SimCounters* ctr,
+           std::conditional_t<PRED, SimPredArgs, SimNoArgs> pa) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ unsigned int taken[COVER_CODES];
+  constexpr unsigned long long EW = PRED ? 5 : 4;  // words of an end record
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   const int W = L.W;
-  uint32_t* const wbase = lds + wave * sim_wave_words(W);
+  uint32_t* const code = lds;  // PRED: both programs, before the waves' words
+  uint32_t* wbase = lds + wave * sim_wave_words(W);
+  if constexpr (PRED) wbase = lds + 2 * PRED_MAX_WORDS + wave * sim_pred_wave_words(W, pa.tc);
   uint32_t* const pall = wbase + 2 * even_words(W);
   FP* const hsrv = reinterpret_cast<FP*>(pall + 32);
-  cover_zero(taken, COVER_CODES);
+  [[maybe_unused]] uint32_t* const stage = wbase + sim_wave_words(W);  // PRED: the children, then their operand files
+  if constexpr (PRED) {
+    for (int k = threadIdx.x; k < pa.n_state; k += blockDim.x) code[k] = pa.prog[k];
+    for (int k = threadIdx.x; k < pa.n_step; k += blockDim.x) code[PRED_MAX_WORDS + k] = pa.prog[PRED_MAX_WORDS + k];
+  }
+  cover_zero(taken, COVER_CODES);  // (its barrier also publishes the programs)
 
   unsigned long long my_steps = 0, my_gen = 0, my_stuck = 0;  // wave-uniform
+  unsigned long long my_state_eval = 0, my_step_eval = 0;     // PRED, wave-uniform
   const int fixed = L.fam[F_RECEIVE];
   for (unsigned int i = blockIdx.x * wpb + wave; i < n_walks; i += gridDim.x * wpb) {
     const unsigned long long w = first + i;
@@ -61,15 +128,16 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
     if (t0 == 0) {
       src = ring_row(cur, w % n_front, W);
     } else {
-      const unsigned long long e = ends[4ull * i + 3];
+      const unsigned long long e = ends[EW * i + 3];
       if ((e >> 32) != SIM_STOP_DEPTH || (uint32_t)e != (uint32_t)t0) continue;  // ended in an earlier launch
-      digest = ends[4ull * i + 2];
+      digest = ends[EW * i + 2];
       src = carry + (unsigned long long)i * W;
     }
     for (int k = lane; k < W; k += 64) a[k] = src[k];
     wave_sync();
     const uint64_t rbase = sim_rng_base(seed, w);
     int len = t0, stop = SIM_STOP_DEPTH;
+    [[maybe_unused]] unsigned long long last_vword = 0;  // PRED: word 4 of a walk that stops on a violation
     for (int t = t0 + 1; t <= t1; t++) {
       // per-parent data: server-record hashes, allLogs' (raft.tla:465) and its fingerprint change
       const FP pfp = parent_setup<NS>(L, a, pall, hsrv, lane);
@@ -77,7 +145,7 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
       const int ncand = min(fixed + 3 * nmsg, SIM_MAX_CAND);  // (the host refuses layouts with more)
       unsigned long long my_mask = 0;  // lane c: ballot of chunk c's in-model successors
       int total = 0, last_chunk = 0;
-      unsigned long long vkey = SIM_NO_VIOLATION;
+      unsigned long long vkey = SIM_NO_VIOLATION, vword = 0;
       DeltaT<NS> d;
       int inst = 0;
       for (int base = 0, c = 0; base < ncand; base += 64, c++) {
@@ -92,10 +160,55 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
         const bool en = enabled_ok(&ctr->flags, d.enabled != 0, d.err);
         my_gen += __popcll(__ballot(en));
         const int bad = en ? check_invariants_v<NS>(L, a, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]) : 0;
-        const unsigned long long mb = __ballot(bad != 0);
+        int sbad = 0, abad = 0;
+        if constexpr (PRED) {
+          const unsigned long long em = __ballot(en);
+          if (em) {  // the enabled lanes' children through the stage, tc at a time
+            const int tc = pa.tc, cs = sim_child_stride(W);
+            int* const files = reinterpret_cast<int*>(stage + tc * cs);
+            const int nen = __popcll(em);
+            const int rank = __popcll(em & ((1ull << lane) - 1ull));
+            const FP cfp = en ? fp_add(pfp, delta_fp<NS>(L, a, d, d.srv >= 0 ? &hsrv[d.srv] : nullptr)) : FP{0, 0};
+            for (int b0 = 0; b0 < nen; b0 += tc) {
+              if (en && rank >= b0 && rank < b0 + tc) {
+                uint32_t* const child = stage + (rank - b0) * cs;
+                int* const file = files + (rank - b0) * PRED_STRIDE;
+                materialize<NS>(L, a, d, pall, cfp, child);
+                if (pa.n_step) {
+                  int err = 0;
+                  abad = pred_eval_rows<NS, true>(L, (const uint32_t*)a, (const uint32_t*)child,
+                                                  (const uint32_t*)(code + PRED_MAX_WORDS), file, &err);
+                  if (err) {
+                    atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
+                    abad = 0;
+                  }
+                  if (step_stutters(a, child)) abad = 0;  // (evaluated first, as [A]_vars: an error stays an error)
+                }
+                if (pa.n_state && d.in_model) {
+                  int err = 0;
+                  sbad = pred_eval<NS>(L, (const uint32_t*)child, (const uint32_t*)code, file, &err);
+                  if (err) {
+                    atomicOr(&ctr->flags, FLAG_SPEC_ERROR);
+                    sbad = 0;
+                  }
+                }
+              }
+              wave_sync();  // the next tile's lanes write the slots this tile's lanes read
+            }
+            if (pa.n_step) my_step_eval += nen;
+            if (pa.n_state) my_state_eval += __popcll(__ballot(en && d.in_model));
+          }
+        }
+        const unsigned long long mb = __ballot((bad | sbad | abad) != 0);
         if (mb && vkey == SIM_NO_VIOLATION) {  // the least violating instance: instances ascend with q
           const int fl = __builtin_ctzll(mb);
-          vkey = sim_viol_key(i, (uint32_t)t, __shfl(inst, fl), __shfl(d.in_model, fl), __shfl(bad, fl));
+          if constexpr (PRED) {  // the key orders by (walk, step, instance); the masks go into the walk's word 4
+            const int vi = __shfl(inst, fl);
+            vkey = sim_viol_key(i, (uint32_t)t, vi, 0, 0);
+            vword = sim_viol_word(vi, __shfl((int)d.in_model, fl), __shfl(bad, fl), __shfl(sbad, fl), __shfl(abad, fl));
+          } else {
+            vkey = sim_viol_key(i, (uint32_t)t, __shfl(inst, fl), __shfl(d.in_model, fl), __shfl(bad, fl));
+          }
         }
         const unsigned long long m = __ballot(en && d.in_model);
         if (lane == c) my_mask = m;
@@ -105,6 +218,7 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
       if (vkey != SIM_NO_VIOLATION) {
         if (lane == 0) atomicMin(&ctr->viol_key, vkey);
         stop = SIM_STOP_VIOLATION;
+        if constexpr (PRED) last_vword = vword;
         break;
       }
       if (total == 0) {  // (not reachable from an in-model state of this spec: Restart is always enabled and stays in-model)
@@ -150,10 +264,11 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
     }
     if (lane == 0) {
       const FP f = row_fp(a);
-      ends[4ull * i] = f.a;
-      ends[4ull * i + 1] = f.b;
-      ends[4ull * i + 2] = digest;
-      ends[4ull * i + 3] = sim_end_word((uint32_t)len, stop);
+      ends[EW * i] = f.a;
+      ends[EW * i + 1] = f.b;
+      ends[EW * i + 2] = digest;
+      ends[EW * i + 3] = sim_end_word((uint32_t)len, stop);
+      if constexpr (PRED) ends[EW * i + 4] = stop == SIM_STOP_VIOLATION ? last_vword : 0;
     }
     if (t1 < depth && stop == SIM_STOP_DEPTH) {  // still running: the next launch continues from this row
       uint32_t* dst = carry + (unsigned long long)i * W;
@@ -165,9 +280,16 @@ k_simulate(Layout L, Ring cur, unsigned long long n_front, unsigned long long se
     if (my_steps) atomicAdd(&ctr->steps, my_steps);
     if (my_gen) atomicAdd(&ctr->generated, my_gen);
     if (my_stuck) atomicAdd(&ctr->stuck, my_stuck);
+    if constexpr (PRED) {
+      if (my_state_eval) atomicAdd(&ctr->state_evaluated, my_state_eval);
+      if (my_step_eval) atomicAdd(&ctr->step_evaluated, my_step_eval);
+    }
   }
   cover_flush(taken, COVER_CODES, ctr->taken);
 }
+
+template <int NS>
+constexpr auto k_simulate_pred = k_simulate<NS, true>;
 
 namespace rtla {
 
@@ -181,7 +303,23 @@ hipError_t launch_simulate(const Layout& L, const Ring& cur, uint64_t n_front, u
   const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)n_walks + wpb - 1) / wpb, (uint64_t)device_cus() * 16);
   RTLA_DISPATCH_N(L, k_simulate, dim3(grid), dim3(64 * wpb), simulate_lds_bytes(L, wpb), st, L, cur,
                   (unsigned long long)n_front, (unsigned long long)seed, (unsigned long long)first, n_walks, t0, t1,
-                  depth, carry, (unsigned long long*)ends, ctr);
+                  depth, carry, (unsigned long long*)ends, ctr, SimNoArgs{});
+  return hipGetLastError();
+}
+
+hipError_t launch_simulate_pred(const Layout& L, const Ring& cur, uint64_t n_front, uint64_t seed, uint64_t first,
+                                uint32_t n_walks, int t0, int t1, int depth, uint32_t* carry, uint64_t* ends,
+                                SimCounters* ctr, const uint32_t* prog, int n_state, int n_step, hipStream_t st) {
+  if (n_state < 0 || n_step < 0 || n_state > PRED_MAX_WORDS || n_step > PRED_MAX_WORDS || !(n_state || n_step))
+    return hipErrorInvalidValue;
+  const SimPredArgs pa{prog, n_state, n_step, sim_tile_children(L.W)};
+  if (pa.tc < 1) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)n_walks + SIM_WPB - 1) / SIM_WPB,
+                                                     (uint64_t)device_cus() * 4 * SIM_PRED_WAVES);
+  const size_t lds = (size_t)(2 * PRED_MAX_WORDS + SIM_WPB * sim_pred_wave_words(L.W, pa.tc)) * sizeof(uint32_t);
+  RTLA_DISPATCH_N(L, k_simulate_pred, dim3(grid), dim3(64 * SIM_WPB), lds, st, L, cur, (unsigned long long)n_front,
+                  (unsigned long long)seed, (unsigned long long)first, n_walks, t0, t1, depth, carry,
+                  (unsigned long long*)ends, ctr, pa);
   return hipGetLastError();
 }
 

@@ -79,6 +79,11 @@ size_t simulate_lds_bytes(const Layout& L, int wpb);
 hipError_t launch_simulate(const Layout& L, const Ring& cur, uint64_t n_front, uint64_t seed, uint64_t first,
                            uint32_t n_walks, int t0, int t1, int depth, uint32_t* carry, uint64_t* ends,
                            SimCounters* ctr, hipStream_t st);
+// The same walks carrying user properties (k_simulate_pred): prog holds the state set's
+// program (n_state words, 0: none) and, at word PRED_MAX_WORDS, the action set's (n_step words); ends: 5 words a walk.
+hipError_t launch_simulate_pred(const Layout& L, const Ring& cur, uint64_t n_front, uint64_t seed, uint64_t first,
+                                uint32_t n_walks, int t0, int t1, int depth, uint32_t* carry, uint64_t* ends,
+                                SimCounters* ctr, const uint32_t* prog, int n_state, int n_step, hipStream_t st);
 // The audit (rtla_kaudit.hip, rtla_audit.h): L.inv_mask evaluated on rows [0, n) of `cur` (succ 0) or on their
 // enabled successors (succ 1); masks (n ints) may be null; ctr: counts added, least violation key kept.
 struct AuditCounters;

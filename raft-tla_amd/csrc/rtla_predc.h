@@ -24,4 +24,13 @@ bool pred_compile(const Layout& L, const char* text, size_t len, rtla_pred* out,
 // definitions are parsed, type-checked and skipped.  A text without an action definition is an error.
 bool pred_compile_step(const Layout& L, const char* text, size_t len, rtla_pred* out, std::string* err);
 
+
+// A set is bound to the row format it was compiled for: the model's bounds and capacities (make_layout derives
+// every offset and width from them).
+inline bool pred_bound_to(const rtla_pred* p, const Layout& L) {
+  const Layout& q = p->L;
+  return q.N == L.N && q.V == L.V && q.T == L.T && q.L == L.L && q.C == L.C && q.M == L.M && q.K == L.K &&
+         q.E == L.E && q.W == L.W;
+}
+
 }  // namespace rtla

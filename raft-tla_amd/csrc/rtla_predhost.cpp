@@ -44,13 +44,6 @@ extern "C" int rtla_pred_name(const rtla_pred* p, int k, char* buf, size_t cap) 
   return (int)p->names[(size_t)k].size();
 }
 
-// A set is bound to the row format it was compiled for: the model's bounds and capacities (make_layout derives
-// every offset and width from them).
-static bool pred_bound_to(const rtla_pred* p, const Layout& L) {
-  const Layout& q = p->L;
-  return q.N == L.N && q.V == L.V && q.T == L.T && q.L == L.L && q.C == L.C && q.M == L.M && q.K == L.K &&
-         q.E == L.E && q.W == L.W;
-}
 // The layout of *c, if `p` was compiled for it and is of the kind the call takes (step: an action set).
 static int pred_layout(const rtla_cfg* c, const rtla_pred* p, bool step, Layout* L) {
   if (int r = layout_from_cfg(c, L)) return r;

@@ -19,8 +19,39 @@
 // End record of a walk: 4 u64 = last state's fingerprint a, b | path digest
 // (sum mod 2^64 of sim_path_term over the states entered) | steps taken |
 // stop code << 32.
+//
+// Walks that carry user properties (rtla_simulate_pred,
+// rtla_sim_replay_pred, rtla_sim_walk_pred).  A simulation may carry a compiled
+// state set P (rtla_pred_compile) and / or a compiled action set A
+// (rtla_pred_compile_step), each of up to 8 definitions and bound to the row
+// layout.  At step t from state s, for every enabled successor u in ascending
+// instance number:
+//   * the built-ins are checked as above (cfg.inv_mask, on parent + delta, in-
+//     and out-of-model);
+//   * A is evaluated on the step (s, u) for every enabled u, in- or
+//     out-of-model, exactly as rtla_pred_step_* does: a definition is false iff
+//     its expression is FALSE and u is not s (step_stutters); the program runs
+//     on a stuttering step all the same, so an evaluation error there is still
+//     an error;
+//   * P is evaluated on u only when u is in-model: the states a BFS would store
+//     and rtla_pred_frontier would audit (out-of-model successors stay the
+//     built-ins' business);
+//   * a successor's spec or row-capacity error, or an evaluation error of
+//     either program, fails the call whatever else was found;
+//   * if any u has a nonzero built-in mask, P mask or A mask the walk ends with
+//     SIM_STOP_VIOLATION at (step t, least such instance); the three masks
+//     reported are that instance's own, not an OR over the step;
+//   * otherwise the pick is unchanged: M[draw(t, |M|)].
+// So a set never changes which walk is taken: every state a walk enters before
+// it ends is the plain walk's, with the same draws, fingerprints and digest
+// terms.  The start row itself is not evaluated (it was not for the built-ins
+// either).  These walks' end record has a fifth word: 0 unless the walk stopped
+// on a violation, then sim_viol_word.  Their violation key orders by (walk,
+// step, instance) alone (its low six bits are 0); the masks are read from that
+// walk's fifth word, so nothing depends on scheduling.
 #pragma once
 #include "rtla_audit.h"
+#include "rtla_step.h"
 #include "rtla_synth.h"
 
 namespace rtla {
@@ -61,12 +92,24 @@ RTLA_HD int sim_key_inst(uint64_t key) { return (int)(key >> 6 & 0xffff); }
 RTLA_HD int sim_key_in_model(uint64_t key) { return (int)(key >> 5 & 1); }
 RTLA_HD int sim_key_mask(uint64_t key) { return (int)(key & INV_ALL); }
 
+// Fifth end word of a walk with user properties that stopped on a violation.
+RTLA_HD uint64_t sim_viol_word(int inst, int in_model, int inv_mask, int state_mask, int step_mask) {
+  return (uint64_t)inst | (uint64_t)(in_model ? 1 : 0) << 16 | (uint64_t)(inv_mask & INV_ALL) << 24 |
+         (uint64_t)(state_mask & 255) << 32 | (uint64_t)(step_mask & 255) << 40;
+}
+RTLA_HD int sim_word_inv_mask(uint64_t w) { return (int)(w >> 24 & 255); }
+RTLA_HD int sim_word_state_mask(uint64_t w) { return (int)(w >> 32 & 255); }
+RTLA_HD int sim_word_step_mask(uint64_t w) { return (int)(w >> 40 & 255); }
+RTLA_HD int sim_word_in_model(uint64_t w) { return (int)(w >> 16 & 1); }
+static_assert(INV_ALL <= 255 && PRED_MAX_DEFS <= 8, "each mask has eight bits of the word");
+
 // Device counters of one rtla_simulate batch.
 struct SimCounters {
   unsigned long long steps, generated, stuck;
   unsigned long long viol_key;  // SIM_NO_VIOLATION, or the least sim_viol_key (atomicMin)
   int flags, pad;
   unsigned long long taken[COVER_CODES];
+  unsigned long long state_evaluated, step_evaluated;  // walks with user properties: evaluations of P / of A
 };
 
 // Host tally of the same quantities.
@@ -75,6 +118,8 @@ struct SimTally {
   uint64_t viol_key = SIM_NO_VIOLATION;
   int flags = 0;
   uint64_t taken[COVER_CODES] = {};
+  uint64_t state_evaluated = 0, step_evaluated = 0;
+  uint64_t viol_word = 0;  // walks with user properties: the fifth end word of viol_key's walk
 };
 
 struct SimEnd {
@@ -84,19 +129,26 @@ struct SimEnd {
   int stop;
   // stop == SIM_STOP_VIOLATION: the violation, at step length + 1
   int viol_inst, viol_sub, viol_mask, viol_in_model;
+  int viol_state_mask, viol_step_mask;  // walks with user properties
 };
 
-// One walk on the host, serially.  buf: 2 * L.W words.  on_state(t, row,
+// One walk on the host, serially.  buf: 3 * L.W words.  on_state(t, row,
 // label, violating) is called for every state entered (label = sub << 16 |
 // instance) and, on a violation, for the violating successor.  rel_walk: the
-// walk's index in its batch (violation key).
+// walk's index in its batch (violation key).  sprog / aprog: the programs of P
+// and A, or null; with either, every enabled successor is materialised once
+// and both programs run on it.
 template <int NS, class F>
 static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uint64_t seed, uint64_t w,
-                                     uint64_t rel_walk, int depth, uint32_t* buf, SimTally& tl, F on_state) {
+                                     uint64_t rel_walk, int depth, uint32_t* buf, SimTally& tl, F on_state,
+                                     const uint32_t* sprog = nullptr, const uint32_t* aprog = nullptr) {
   constexpr int NR = NS ? NS : NMAX;
   const int W = L.W;
+  const bool pred = sprog || aprog;
   uint32_t* cur = buf;
   uint32_t* nxt = buf + W;
+  uint32_t* const stage = buf + 2 * W;
+  int file[PRED_FILE];
   uint32_t pall[33];
   uint16_t model[SIM_MAX_CAND];
   for (int k = 0; k < W; k++) cur[k] = start[k];
@@ -111,9 +163,33 @@ static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uin
     for_each_successor<NS>(L, cur, tl.flags, [&](int inst, const auto& d) {
       tl.generated++;
       const int bad = check_invariants_v<NS>(L, cur, d.srv, d.rec[0], d.rec[1], d.elec, d.erec[0]);
-      if (bad && !violated) {
+      int sbad = 0, abad = 0;
+      if (pred) {
+        materialize<NS>(L, cur, d, pall, fp_add(pfp, delta_fp<NS>(L, cur, d)), stage);
+        if (aprog) {
+          int err = 0;
+          abad = pred_eval_rows<NS, true>(L, (const uint32_t*)cur, (const uint32_t*)stage, aprog, file, &err);
+          tl.step_evaluated++;
+          if (err) {
+            tl.flags |= FLAG_SPEC_ERROR;
+            abad = 0;
+          }
+          if (step_stutters(cur, stage)) abad = 0;  // (evaluated first, as [A]_vars: an error stays an error)
+        }
+        if (sprog && d.in_model) {
+          int err = 0;
+          sbad = pred_eval<NS>(L, (const uint32_t*)stage, sprog, file, &err);
+          tl.state_evaluated++;
+          if (err) {
+            tl.flags |= FLAG_SPEC_ERROR;
+            sbad = 0;
+          }
+        }
+      }
+      if ((bad | sbad | abad) && !violated) {
         violated = true;
         e.viol_inst = inst; e.viol_sub = d.sub; e.viol_mask = bad; e.viol_in_model = d.in_model;
+        e.viol_state_mask = sbad; e.viol_step_mask = abad;
         const FP cfp = fp_add(pfp, delta_fp<NS>(L, cur, d));
         materialize<NS>(L, cur, d, pall, cfp, nxt);
       }
@@ -121,8 +197,12 @@ static inline SimEnd sim_walk_serial(const Layout& L, const uint32_t* start, uin
     });
     if (violated) {
       e.stop = SIM_STOP_VIOLATION;
-      const uint64_t key = sim_viol_key(rel_walk, (uint32_t)t, e.viol_inst, e.viol_in_model, e.viol_mask);
-      if (key < tl.viol_key) tl.viol_key = key;
+      const uint64_t key = pred ? sim_viol_key(rel_walk, (uint32_t)t, e.viol_inst, 0, 0)
+                                : sim_viol_key(rel_walk, (uint32_t)t, e.viol_inst, e.viol_in_model, e.viol_mask);
+      if (key < tl.viol_key) {
+        tl.viol_key = key;
+        tl.viol_word = sim_viol_word(e.viol_inst, e.viol_in_model, e.viol_mask, e.viol_state_mask, e.viol_step_mask);
+      }
       on_state(t, (const uint32_t*)nxt, (int32_t)(e.viol_sub << 16 | e.viol_inst), true);
       break;
     }

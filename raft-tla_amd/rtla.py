@@ -72,6 +72,11 @@ class _SimStats(C.Structure):
                 ("status", C.c_int32), ("flags", C.c_int32), ("taken", C.c_uint64 * 16)]
 
 
+class _SimPredStats(C.Structure):
+    _fields_ = [("state_evaluated", C.c_uint64), ("step_evaluated", C.c_uint64), ("viol_inv_mask", C.c_int32),
+                ("viol_state_mask", C.c_int32), ("viol_step_mask", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _AuditStats(C.Structure):
     _fields_ = [("audited", C.c_uint64), ("evaluated", C.c_uint64), ("counts", C.c_uint64 * 8),
                 ("kernel_ms", C.c_double), ("row_bytes", C.c_uint64), ("viol_index", C.c_uint64),
@@ -137,6 +142,13 @@ def _load():
                                       C.c_int32, C.c_int, P(C.c_uint64), P(_SimStats)]),
         "rtla_sim_walk": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_uint64, C.c_uint64, C.c_int32, P(C.c_uint32),
                                     P(C.c_int32), C.c_size_t, P(C.c_size_t)]),
+        "rtla_simulate_pred": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p,
+                                         C.c_void_p, P(C.c_uint64), P(_SimStats), P(_SimPredStats)]),
+        "rtla_sim_replay_pred": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64,
+                                           C.c_int32, C.c_int, C.c_void_p, C.c_void_p, P(C.c_uint64), P(_SimStats),
+                                           P(_SimPredStats)]),
+        "rtla_sim_walk_pred": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p,
+                                         C.c_void_p, P(C.c_uint32), P(C.c_int32), C.c_size_t, P(C.c_size_t)]),
         "rtla_check_batch": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_int32, C.c_int32, P(C.c_int32),
                                        P(C.c_uint64)]),
         "rtla_check_replay": (C.c_int, [P(_Cfg), P(C.c_uint32), C.c_size_t, C.c_int32, C.c_int32, C.c_int,
@@ -181,7 +193,8 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_check_replay", "rtla_check_frontier", "rtla_fpset_probe", "rtla_pred_compile", "rtla_pred_free",
             "rtla_pred_count", "rtla_pred_name", "rtla_pred_replay", "rtla_pred_batch", "rtla_pred_frontier",
             "rtla_pred_compile_step", "rtla_pred_is_step", "rtla_pred_step_replay", "rtla_pred_step_batch",
-            "rtla_pred_step_frontier", "rtla_init_rows"]
+            "rtla_pred_step_frontier", "rtla_init_rows", "rtla_simulate_pred", "rtla_sim_replay_pred",
+            "rtla_sim_walk_pred"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -266,22 +279,47 @@ class SimResult:
     viol_mask: int = 0
     viol_in_model: bool = True
     taken: dict = field(default_factory=dict)   # steps taken per coverage name
-    ends: Optional[List[Tuple[int, int, int, int, int]]] = None  # per walk: (fp a, fp b, path digest, length, stop)
+    ends: Optional[List[Tuple[int, ...]]] = None  # per walk: (fp a, fp b, path digest, length, stop)
+    # walks that carry user properties (predicates= / actions=): ends are 6-tuples, the five fields plus word 4
+    # (instance | in_model << 16 | built-in mask << 24 | state mask << 32 | step mask << 40; 0: no violation);
+    # violation is the ", "-joined names of every false thing of the reported successor: built-ins, state
+    # definitions, action definitions
+    viol_state_mask: int = 0       # its false state definitions (bit k = predicates.names[k])
+    viol_step_mask: int = 0        # its false action definitions
+    state_evaluated: int = 0       # evaluations of the state set (in-model successors)
+    step_evaluated: int = 0        # evaluations of the action set (== generated)
 
 
-def _sim_result(rc: int, st: _SimStats, ends, n: int) -> SimResult:
+def _sim_result(rc: int, st: _SimStats, ends, n: int, pst=None, predicates=None, actions=None) -> SimResult:
     res = SimResult(status=rc, walks=st.walks, steps=st.steps, generated=st.generated, stuck=st.stuck,
                     kernel_ms=st.kernel_ms, taken={COVER_NAMES[k]: st.taken[k] for k in range(len(COVER_NAMES))})
+    if pst is not None:
+        res.state_evaluated, res.step_evaluated = pst.state_evaluated, pst.step_evaluated
     if rc == VIOLATION:
         names = [nm for nm, b in INV_BITS.items() if st.viol_mask & b]
         res.violation = names[0] if names else None
         res.viol_walk, res.viol_step, res.viol_inst = st.viol_walk, st.viol_step, st.viol_inst
         res.viol_mask, res.viol_in_model = st.viol_mask, bool(st.viol_in_model)
+        if pst is not None:
+            res.viol_state_mask, res.viol_step_mask = pst.viol_state_mask, pst.viol_step_mask
+            names += predicates.names_of(pst.viol_state_mask) if predicates is not None else []
+            names += actions.names_of(pst.viol_step_mask) if actions is not None else []
+            res.violation = ", ".join(names)
     if ends is not None:
-        m = min(n, st.walks)
-        res.ends = [(ends[4 * k], ends[4 * k + 1], ends[4 * k + 2], ends[4 * k + 3] & 0xFFFFFFFF, ends[4 * k + 3] >> 32)
+        m, ew = min(n, st.walks), 4 if pst is None else 5
+        res.ends = [(ends[ew * k], ends[ew * k + 1], ends[ew * k + 2], ends[ew * k + 3] & 0xFFFFFFFF,
+                     ends[ew * k + 3] >> 32) + ((ends[ew * k + 4],) if pst is not None else ())
                     for k in range(m)]
     return res
+
+
+def _set_handle(s, step: bool):
+    """The handle of an optional set for the *_pred calls (None: NULL); the library checks its kind and layout."""
+    if s is None:
+        return None
+    if not isinstance(s, Predicates) or s._h is None:
+        raise RtlaError(E_ARG, "actions=" if step else "predicates=")
+    return s._h
 
 
 def _flat_rows(rows, w: int):
@@ -297,13 +335,23 @@ def _flat_rows(rows, w: int):
 
 
 def sim_replay(cfg: Config, start_rows, n_walks: int, depth: int, seed: int = SIM_SEED,
-               first: int = 0, threads: int = 0, ends: bool = True) -> SimResult:
+               first: int = 0, threads: int = 0, ends: bool = True, predicates=None, actions=None) -> SimResult:
     """Checker.simulate's walks recomputed on the host (rtla_sim_replay): walk
     w starts at start_rows[w mod len(start_rows)] (a list of rows, or the flat
-    array of Checker.frontier_flat).  No GPU, no context."""
+    array of Checker.frontier_flat).  No GPU, no context.  predicates /
+    actions: as Checker.simulate's (rtla_sim_replay_pred)."""
     cc = cfg.c()
     w = row_words(cfg)
     flat, n_start = _flat_rows(start_rows, w)
+    if predicates is not None or actions is not None:
+        buf = (C.c_uint64 * max(1, 5 * n_walks))() if ends else None
+        st, pst = _SimStats(), _SimPredStats()
+        rc = _lib.rtla_sim_replay_pred(C.byref(cc), flat, n_start, seed, first, n_walks, depth, threads,
+                                       _set_handle(predicates, False), _set_handle(actions, True), buf, C.byref(st),
+                                       C.byref(pst))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_sim_replay_pred", st.flags)
+        return _sim_result(rc, st, buf, n_walks, pst, predicates, actions)
     buf = (C.c_uint64 * max(1, 4 * n_walks))() if ends else None
     st = _SimStats()
     rc = _lib.rtla_sim_replay(C.byref(cc), flat, n_start, seed, first, n_walks, depth, threads, buf,
@@ -313,10 +361,12 @@ def sim_replay(cfg: Config, start_rows, n_walks: int, depth: int, seed: int = SI
     return _sim_result(rc, st, buf, n_walks)
 
 
-def sim_walk(cfg: Config, start_row: Sequence[int], walk: int, depth: int, seed: int = SIM_SEED):
+def sim_walk(cfg: Config, start_row: Sequence[int], walk: int, depth: int, seed: int = SIM_SEED,
+             predicates=None, actions=None):
     """One walk from start_row on the host (rtla_sim_walk): (violating, steps)
     with steps = [(instance, receive-sub, row)] of the states it enters and,
-    last when `violating`, of its violating successor."""
+    last when `violating`, of its violating successor.  predicates / actions:
+    as Checker.simulate's (rtla_sim_walk_pred)."""
     cc = cfg.c()
     w = row_words(cfg)
     arr = (C.c_uint32 * w)(*start_row)
@@ -324,7 +374,14 @@ def sim_walk(cfg: Config, start_row: Sequence[int], walk: int, depth: int, seed:
     rows = (C.c_uint32 * (cap * w))()
     labels = (C.c_int32 * cap)()
     n = C.c_size_t(0)
-    rc = _check(_lib.rtla_sim_walk(C.byref(cc), arr, seed, walk, depth, rows, labels, cap, C.byref(n)), "rtla_sim_walk")
+    if predicates is not None or actions is not None:
+        rc = _lib.rtla_sim_walk_pred(C.byref(cc), arr, seed, walk, depth, _set_handle(predicates, False),
+                                     _set_handle(actions, True), rows, labels, cap, C.byref(n))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_sim_walk_pred", CAP_SPEC_ERROR if rc == E_SPEC else 0)
+    else:
+        rc = _check(_lib.rtla_sim_walk(C.byref(cc), arr, seed, walk, depth, rows, labels, cap, C.byref(n)),
+                    "rtla_sim_walk")
     return rc == VIOLATION, [(labels[k] & 0xFFFF, (labels[k] >> 16) & 0x7FFF, list(rows[k * w:(k + 1) * w]))
                              for k in range(n.value)]
 
@@ -883,14 +940,32 @@ class Checker:
         return Level(0, st.frontier, st.new_states, st.generated, st.seconds, st.kernel_ms, st.probes, st.row_bytes,
                      st.expand_ms)
 
-    def simulate(self, n_walks: int, depth: int, seed: int = SIM_SEED, first: int = 0, ends: bool = False) -> SimResult:
+    def simulate(self, n_walks: int, depth: int, seed: int = SIM_SEED, first: int = 0, ends: bool = False,
+                 predicates=None, actions=None) -> SimResult:
         """TLC -simulate: walks first .. first + n_walks - 1 of up to `depth`
         steps from the states of the level last produced (walk w starts at
         frontier row w mod frontier_size()).  The BFS is left untouched; after
-        a VIOLATION result, violation() and trace() give the counterexample."""
+        a VIOLATION result, violation() and trace() give the counterexample.
+        predicates / actions: a compiled state set / action set the walks carry
+        (rtla_simulate_pred): the action set is checked
+        on every step out of every state a walk visits, the state set on every
+        in-model successor, and a walk ends at the first successor on which a
+        built-in invariant or a definition is false.  The sets never change
+        which walk is taken."""
+        self._pred_viol = None
+        if predicates is not None or actions is not None:
+            buf = (C.c_uint64 * max(1, 5 * n_walks))() if ends else None
+            st, pst = _SimStats(), _SimPredStats()
+            rc = _lib.rtla_simulate_pred(self._h, seed, first, n_walks, depth, _set_handle(predicates, False),
+                                         _set_handle(actions, True), buf, C.byref(st), C.byref(pst))
+            if rc < 0:
+                raise RtlaError(rc, "rtla_simulate_pred", st.flags)
+            res = _sim_result(rc, st, buf, n_walks, pst, predicates, actions)
+            if rc == VIOLATION:
+                self._pred_viol = res.violation.split(", ")
+            return res
         buf = (C.c_uint64 * max(1, 4 * n_walks))() if ends else None
         st = _SimStats()
-        self._pred_viol = None
         rc = _lib.rtla_simulate(self._h, seed, first, n_walks, depth, buf, C.byref(st))
         if rc < 0:
             raise RtlaError(rc, "rtla_simulate", st.flags)
