@@ -463,6 +463,58 @@ int rtla_pred_step_batch(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t
                          uint64_t *counts, uint64_t *evaluated);
 int rtla_pred_step_frontier(rtla_ctx *ctx, const rtla_pred *p, rtla_audit_stats *out);
 
+/* User-defined CONSTRAINTs (TLC: an operator added to MC.tla and named under
+ * CONSTRAINT; DESIGN.md section 16, examples: specs/MCConstraints.tla).
+ * rtla_pred_constrain evaluates the state set `p` on every row of the level
+ * last produced and keeps row g iff every definition is TRUE on it.  Kept rows
+ * keep their order and become rows 0 .. kept-1 of the same level, in place in
+ * the arena, their parent records with them; the frontier shrinks to `kept`
+ * and distinct_total by `dropped`, so every later count, digest, trace, audit,
+ * simulation, checkpoint and rtla_step sees the kept rows only.  Call it after
+ * rtla_init / rtla_init_rows / rtla_step (and after auditing user invariants
+ * on the unfiltered level, as TLC checks them on states it then discards) and
+ * before anything reads the level as a frontier.  Returns RTLA_OK, or RTLA_DONE
+ * when no row is kept (the search is finished).
+ * Not corrected: the fingerprint set keeps the dropped states' keys (a dropped
+ * state met again is "seen"; its load is the pre-drop one), and
+ * rtla_coverage's per-action distinct counts still include dropped states.
+ * Preconditions: rtla_check_frontier's (else RTLA_E_STATE).  A step set or a
+ * set compiled for another layout: RTLA_E_ARG.  An evaluation error on any row:
+ * RTLA_E_SPEC, with the frontier, parent records and totals exactly as before
+ * the call.  A HIP failure while rows move ends the search.  Under SYMMETRY the
+ * constraint must be symmetric under server permutation, as TLC requires.
+ * The compaction runs in chunks of RTLA_CONSTRAIN_CHUNK rows (environment;
+ * rounded up to 64; default 2^20) through a staging buffer of that many rows,
+ * allocated at first use and freed by rtla_close. */
+typedef struct {
+    int32_t level;           /* the level pruned (rtla_level_stats.level of the call that produced it) */
+    int32_t status;          /* the call's return value */
+    uint64_t examined;       /* rows of the level before the call */
+    uint64_t kept;           /* rows on which every definition is TRUE: the frontier now */
+    uint64_t dropped;        /* examined - kept */
+    uint64_t counts[8];      /* per definition: rows on which it is FALSE */
+    uint64_t start;          /* arena row of the level's first state (the level wraps if start + examined exceeds
+                                the arena's rows) */
+    double eval_ms;          /* device time of the evaluation and the keep bitmap */
+    double move_ms;          /* device time of the compaction (0 when nothing was dropped: nothing is written) */
+    uint64_t distinct_total; /* after the drop */
+    int32_t flags;           /* on RTLA_E_SPEC: RTLA_CAP_SPEC_ERROR */
+    int32_t reserved;
+} rtla_constrain_stats;
+int rtla_pred_constrain(rtla_ctx *ctx, const rtla_pred *p, rtla_constrain_stats *out);
+/* The same pass, stateless (test-sized inputs): the n rows are laid into a
+ * device ring of ring_cap rows from row ring_start on, wrapping at its end if
+ * they must (ring_cap and ring_start multiples of 64, ring_start < ring_cap,
+ * ring_cap >= n rounded up to 64), `parents` (n u64, in/out) stands for the
+ * parent records, and the same kernels run with chunks of `chunk` rows
+ * (rounded up to 64; 0: the default).  out_rows (room for n rows) gets the kept
+ * rows in order, parents[0 .. *kept) their entries, counts (may be NULL; 8 u64)
+ * the rows on which each definition is false.  On any error no output is
+ * written. */
+int rtla_constrain_batch(const rtla_cfg *cfg, const rtla_pred *p, const uint32_t *rows, size_t n, uint64_t ring_cap,
+                         uint64_t ring_start, uint64_t chunk, uint32_t *out_rows, uint64_t *parents, size_t *kept,
+                         uint64_t *counts);
+
 /* Diagnostic (performance analysis only): re-expand the current frontier
  * `reps` times with the level kernel's experiment switches `xflags` (XF_*
  * in raft-tla_amd/csrc/rtla_device.h: e.g. 1 = no fingerprint-set probe,

@@ -25,6 +25,9 @@
 // `Name == [][A]_vars` of FILE: it is checked on every
 // step out of every level; -audit may name one too (the steps out of the last level).
 // With -simulate the same sets go into the walks.
+// A name under CONSTRAINT(S) beside StateConstraint is a state definition of FILE
+// (specs/MCConstraints.tla) and prunes every level right after its invariants
+// were checked; not with -simulate.
 //
 // SPEC.tla is either the reference's raft.tla (sha256 checked: the semantics
 // are compiled into the kernels, not parsed) or a wrapper module that
@@ -239,7 +242,8 @@ void usage() {
           "          -audit may name beside the built-in invariants; checked on every level of the search (-gpus 1).\n"
           "          Its action definitions `Name == [][A]_vars` (specs/MCActions.tla) may be named under\n"
           "          PROPERTY / PROPERTIES, and are then checked on every step out of every level, or under -audit\n"
-          "          (the steps out of the last level)\n"
+          "          (the steps out of the last level).  A state definition (specs/MCConstraints.tla) may be named\n"
+          "          under CONSTRAINT(S) beside StateConstraint: it prunes every level of the search (no -simulate)\n"
           "  -audit: when the BFS stops (exhausted, out of capacity, or after -bfs-levels K) evaluate the named\n"
           "  invariants -- any of the specification's, not only the cfg's -- over the states of the last level;\n"
           "  one GPU only.\n");
@@ -695,12 +699,35 @@ int main(int argc, char** argv) {
     }
     audit_mask |= invariant_bit(inv);
   }
-  for (auto& k : cf.constraints) {
-    if (k != "StateConstraint" || !defined(k)) {
-      printf("Error: The constraint %s specified in the configuration file is not defined in the specification.\n",
-             k.c_str());
-      return 150;
+  // CONSTRAINT names StateConstraint (the compiled-in bounds); any further name is a state definition of the
+  // -predicates file, and prunes every level on the GPU (rtla_pred_constrain)
+  std::vector<std::string> user_cons;
+  bool built_in_constraint = false;
+  {
+    std::vector<std::string> state_names;
+    if (!pred_file.empty()) {
+      bool pf_ok = false;
+      state_names = definitions_of_kind(read_file(pred_file, &pf_ok), false);
     }
+    for (auto& k : cf.constraints) {
+      if (k == "StateConstraint" && defined(k)) { built_in_constraint = true; continue; }
+      if (is_action(k)) {
+        printf("Error: The constraint %s is an action definition; a CONSTRAINT is a state predicate "
+               "(ACTION_CONSTRAINT is not supported by this checker).\n", k.c_str());
+        return 150;
+      }
+      if (std::find(state_names.begin(), state_names.end(), k) == state_names.end()) {
+        printf("Error: The constraint %s specified in the configuration file is not defined in the specification.\n",
+               k.c_str());
+        return 150;
+      }
+      if (std::find(user_cons.begin(), user_cons.end(), k) == user_cons.end()) user_cons.push_back(k);
+    }
+  }
+  if (!user_cons.empty() && simulate) {
+    printf("Error: -simulate with a user-defined CONSTRAINT (%s) is not supported: the random walks do not honour "
+           "constraints, and are not run unconstrained in their place.\n", user_cons[0].c_str());
+    return 150;
   }
   if (!cf.symmetry.empty()) {
     if (!wrapper || cf.symmetry != "Perms") {
@@ -710,7 +737,7 @@ int main(int argc, char** argv) {
     }
     c.symmetry = 1;  // Perms == Permutations(Server) (specs/MC.tla)
   }
-  if (cf.constraints.empty()) {
+  if (!built_in_constraint) {
     printf("Error: no CONSTRAINT: raft.tla's state space is infinite (Timeout raft.tla:180 and Send raft.tla:106-110 "
            "are unbounded); add CONSTRAINT StateConstraint from specs/MC.tla.\n");
     return 151;
@@ -751,14 +778,32 @@ int main(int argc, char** argv) {
   rtla_pred* audit_preds = user_audit.empty() ? nullptr : load_predicates(&c, pred_file, user_audit);
   rtla_pred* actions = cf.properties.empty() ? nullptr : load_actions(&c, pred_file, cf.properties);
   rtla_pred* audit_acts = audit_actions.empty() ? nullptr : load_actions(&c, pred_file, audit_actions);
+  rtla_pred* constraint = user_cons.empty() ? nullptr : load_predicates(&c, pred_file, user_cons);
+  if (constraint) {
+    std::string line = "Constraining the search by: ";
+    for (int k = 0; k < rtla_pred_count(constraint); k++) line += (k ? ", " : "") + pred_name(constraint, k);
+    printf("%s.\n", line.c_str());
+  }
   bool pred_violation = false;  // the violation reported is a predicate set's: its mask holds definition bits
   const rtla_pred* viol_set = nullptr;
   // user-defined invariants: the level just produced is audited in place (rtla_pred_frontier); then the action
   // properties on the steps out of it (rtla_pred_step_frontier), so every step out of every reachable in-model
-  // state is checked before the next level is produced
-  auto check_level = [&](rtla_ctx* x, int st_level, uint64_t new_states) -> int {
-    if (st_level != RTLA_OK || new_states == 0) return st_level;
-    for (const rtla_pred* set : {(const rtla_pred*)preds, (const rtla_pred*)actions}) {
+  // state is checked before the next level is produced.  Between the two the user CONSTRAINT prunes the level
+  // (the invariants see it whole, as TLC checks them on states it then discards; the steps are the kept rows'),
+  // and the level's figures become the post-drop ones.
+  auto check_level = [&](rtla_ctx* x, int st_level, rtla_level_stats& lv) -> int {
+    if (st_level != RTLA_OK || lv.new_states == 0) return st_level;
+    const rtla_pred* const sets[2] = {preds, actions};
+    for (int q = 0; q < 2; q++) {
+      const rtla_pred* const set = sets[q];
+      if (q == 1 && constraint) {
+        rtla_constrain_stats cs;
+        const int rc = rtla_pred_constrain(x, constraint, &cs);
+        if (rc < 0) return rc;
+        lv.new_states = cs.kept;
+        lv.distinct_total = cs.distinct_total;
+        if (rc == RTLA_DONE) return rc;
+      }
       if (!set) continue;
       const int rc = rtla_pred_is_step(set) ? rtla_pred_step_frontier(x, set, nullptr) : rtla_pred_frontier(x, set, nullptr);
       if (rc == RTLA_VIOLATION) { pred_violation = true; viol_set = set; }
@@ -790,7 +835,7 @@ int main(int argc, char** argv) {
   } else {
     st = rtla_init(ctx, &ls);
     printf("Finished computing initial states: 1 distinct state generated at %s.\n", now_str().c_str());
-    st = check_level(ctx, st, 1);
+    st = check_level(ctx, st, ls);
   }
   auto last_progress = t0, last_ckpt = t0;
   // With several ranks the checkpoint (a collective) must be decided alike
@@ -802,7 +847,7 @@ int main(int argc, char** argv) {
   while (st == RTLA_OK && !(stop_at_level && ls.level >= bfs_levels)) {
     st = rtla_step(ctx, &ls);
     if (st < 0) break;
-    st = check_level(ctx, st, ls.new_states);
+    st = check_level(ctx, st, ls);
     if (st < 0) break;
     dev_s += ls.kernel_ms / 1e3;
     const double since = world > 1 ? dev_s - dev_ckpt

@@ -5,6 +5,7 @@
 //   rtla_simhost.cpp  random-walk simulation
 //   rtla_audit.cpp    passes over rows outside the search (batch, host replay, frontier), and the invariant audit
 //   rtla_predhost.cpp user-defined predicates: the rtla_pred_* ABI over the compiler (rtla_pred.cpp) and those passes
+//   rtla_constrain.cpp user-defined CONSTRAINTs: the level just produced pruned by a state set (rtla_kconstrain.hip)
 //   rtla_rows.cpp     the context-free row API, synthetic and probe micro-benchmarks
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,6 +96,24 @@ struct AuditState {
   int inst = -1, mask = 0, in_model = 0;  // inst >= 0: the violating successor's action instance
 };
 
+// rtla_pred_constrain's device buffers and events (allocated at first use, freed at close; rtla_constrain.cpp)
+namespace rtla {
+struct ConstrainTotals;
+}
+struct ConstrainBufs {
+  uint32_t* stage = nullptr;      // [rows * W + 4] a chunk's kept rows on their way back into the ring
+  uint64_t* stage_par = nullptr;  // [rows] and their parent records
+  int* masks = nullptr;           // [rows] k_pred_state's per-row masks of one chunk
+  uint64_t* keep = nullptr;       // [keep_words] the level's keep bitmap: one u64 per group of 64 rows
+  uint32_t* offs = nullptr;       // [rows / 64] a chunk's kept rows before each of its groups
+  ConstrainTotals* tot = nullptr;
+  AuditCounters* ctr = nullptr;
+  uint32_t* prog = nullptr;       // the program's device copy (PRED_MAX_WORDS words)
+  uint64_t rows = 0, keep_words = 0;  // rows: the chunk size R the buffers were made for
+  int W = 0;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
 // device scratch of the all-reduces: sums at [0, RED_MAX_AT), maxima after
 constexpr int RED_WORDS = 256, RED_MAX_AT = 192;
 
@@ -132,6 +151,7 @@ struct rtla_ctx {
   bool seeded = false;          // the roots are rtla_init_rows's (no checkpoint holds them)
   SimState sim;
   AuditState audit;
+  ConstrainBufs constrain;
 
   Shard* local(int id) {  // the shard with this global id, if this process holds it
     for (auto& s : sh)
@@ -224,6 +244,8 @@ AuditCounters audit_zero();
 int audit_batch(const Layout& L, const uint32_t* rows, size_t n, const AuditLaunch& launch, int32_t* masks,
                 uint64_t* counts, uint64_t* evaluated = nullptr);
 int audit_frontier(rtla_ctx* x, int succ, const AuditLaunch& launch, rtla_audit_stats* out);
+// rtla_constrain.cpp
+void constrain_free(ConstrainBufs& b);
 // rtla_rows.cpp
 int text_threads(int want);
 

@@ -152,6 +152,7 @@ extern "C" void rtla_close(rtla_ctx* x) {
   if (x->audit.prog) (void)hipFree(x->audit.prog);
   if (x->audit.ev0) (void)hipEventDestroy(x->audit.ev0);
   if (x->audit.ev1) (void)hipEventDestroy(x->audit.ev1);
+  constrain_free(x->constrain);
   comm_close(x);
   if (x->stream) (void)hipStreamDestroy(x->stream);
   delete x;

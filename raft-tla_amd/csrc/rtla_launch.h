@@ -97,6 +97,17 @@ hipError_t launch_pred(const Layout& L, const Ring& cur, uint64_t n, const uint3
 // the OR over each row's steps; the key carries the step's instance.
 hipError_t launch_pred_step(const Layout& L, const Ring& cur, uint64_t n, const uint32_t* prog, int nwords,
                             int* masks, AuditCounters* ctr, hipStream_t st);
+// The constraint pass (rtla_kconstrain.hip, rtla_constrain.h).  launch_constrain_pack:
+// masks[0, n) of launch_pred -> keep[g], the ballot of "mask == 0" over group g of 64 rows; the rows with a mask
+// are added to tot->dropped.  launch_constrain_move: one chunk -- rows [first, first + rows) of `cur`, first a
+// multiple of 64, keep and offs (rows / 64 words, scratch) the chunk's own -- compacted in place behind the
+// chunks before it: scan, gather into stage / stage_par (rows * W + 4 words, rows records), copy-back; parents:
+// the level's records (row g's at parents[g]).  Chunks are enqueued in ascending order on one stream.
+struct ConstrainTotals;
+hipError_t launch_constrain_pack(const int* masks, uint64_t n, uint64_t* keep, ConstrainTotals* tot, hipStream_t st);
+hipError_t launch_constrain_move(const Ring& cur, int W, uint64_t first, uint64_t rows, const uint64_t* keep,
+                                 uint32_t* offs, uint64_t* parents, uint32_t* stage, uint64_t* stage_par,
+                                 ConstrainTotals* tot, hipStream_t st);
 hipError_t launch_insert_remote(const uint64_t* recv_fp, const uint64_t* counts, int nshard, uint64_t cap,
                                 uint64_t* table, int tlog2, uint32_t* ans, DevCounters* ctr, uint64_t max_count,
                                 hipStream_t st);

@@ -84,6 +84,13 @@ class _AuditStats(C.Structure):
                 ("status", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _ConstrainStats(C.Structure):
+    _fields_ = [("level", C.c_int32), ("status", C.c_int32), ("examined", C.c_uint64), ("kept", C.c_uint64),
+                ("dropped", C.c_uint64), ("counts", C.c_uint64 * 8), ("start", C.c_uint64),
+                ("eval_ms", C.c_double), ("move_ms", C.c_double), ("distinct_total", C.c_uint64),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("librtla.so not built at %s (run `make -C raft-tla_amd` or "
@@ -171,6 +178,9 @@ def _load():
         "rtla_pred_step_batch": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, P(C.c_int32),
                                            P(C.c_uint64), P(C.c_uint64)]),
         "rtla_pred_step_frontier": (C.c_int, [C.c_void_p, C.c_void_p, P(_AuditStats)]),
+        "rtla_pred_constrain": (C.c_int, [C.c_void_p, C.c_void_p, P(_ConstrainStats)]),
+        "rtla_constrain_batch": (C.c_int, [P(_Cfg), C.c_void_p, P(C.c_uint32), C.c_size_t, C.c_uint64, C.c_uint64,
+                                           C.c_uint64, P(C.c_uint32), P(C.c_uint64), P(C.c_size_t), P(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -194,7 +204,7 @@ EXPORTED = ["rtla_open", "rtla_close", "rtla_comm_id", "rtla_init", "rtla_reset"
             "rtla_pred_count", "rtla_pred_name", "rtla_pred_replay", "rtla_pred_batch", "rtla_pred_frontier",
             "rtla_pred_compile_step", "rtla_pred_is_step", "rtla_pred_step_replay", "rtla_pred_step_batch",
             "rtla_pred_step_frontier", "rtla_init_rows", "rtla_simulate_pred", "rtla_sim_replay_pred",
-            "rtla_sim_walk_pred"]
+            "rtla_sim_walk_pred", "rtla_pred_constrain", "rtla_constrain_batch"]
 
 SYNTH_SEED = 0x5AF72025  # the synthetic microbench's PRNG seed
 
@@ -549,6 +559,46 @@ def pred_step_batch(actions: Predicates, rows):
     return _pred_rows(_lib.rtla_pred_step_batch, "rtla_pred_step_batch", actions, rows, steps=True)
 
 
+@dataclass
+class ConstrainResult:
+    """One Checker.constrain() call (rtla_constrain_stats)."""
+    status: int = OK               # OK, or DONE when no row is kept
+    level: int = 0
+    examined: int = 0              # rows of the level before the call
+    kept: int = 0                  # rows on which every definition is TRUE: the frontier now
+    dropped: int = 0
+    counts: dict = field(default_factory=dict)  # definition name -> rows on which it is false
+    start: int = 0                 # arena row of the level's first state
+    eval_ms: float = 0.0
+    move_ms: float = 0.0
+    distinct_total: int = 0        # after the drop
+
+
+def constrain_batch(preds: Predicates, rows, side=None, ring_cap: int = 0, ring_start: int = 0, chunk: int = 0):
+    """The constraint pass on host rows (rtla_constrain_batch: the kernels of
+    Checker.constrain, stateless): the rows are laid into a device ring of
+    ring_cap rows (0: just room for them) from row ring_start on, wrapping if
+    they must, and compacted in chunks of `chunk` rows (0: the default).
+    Returns (kept rows in order, the kept entries of `side` -- one integer per
+    row, default range(n) -- and counts[name], the rows on which it is false).
+    An evaluation error raises RtlaError(E_SPEC)."""
+    cc = preds.cfg.c()
+    w = row_words(preds.cfg)
+    flat, n = _flat_rows(rows, w)
+    par = (C.c_uint64 * max(1, n))(*(range(n) if side is None else side))
+    out = (C.c_uint32 * max(1, n * w))()
+    kept = C.c_size_t(0)
+    counts = (C.c_uint64 * 8)()
+    cap = ring_cap or ((n + 63) // 64 * 64 or 64)
+    rc = _lib.rtla_constrain_batch(C.byref(cc), preds._h, flat, n, cap, ring_start, chunk, out, par, C.byref(kept),
+                                   counts)
+    if rc < 0:
+        raise RtlaError(rc, "rtla_constrain_batch", CAP_SPEC_ERROR if rc == E_SPEC else 0)
+    k = kept.value
+    return ([list(out[i * w:(i + 1) * w]) for i in range(k)], list(par[:k]),
+            {nm: counts[d] for d, nm in enumerate(preds.names)})
+
+
 def row_words(cfg: Config) -> int:
     cc = cfg.c()
     return _check(_lib.rtla_row_words(C.byref(cc)), "rtla_row_words")
@@ -805,19 +855,24 @@ class Checker:
         return self.status
 
     def run(self, max_levels: int = 100000, predicates: Optional[Predicates] = None,
-            actions: Optional[Predicates] = None, roots=None) -> int:
+            actions: Optional[Predicates] = None, roots=None, constraint: Optional[Predicates] = None) -> int:
         """BFS until the search ends, a violation or max_levels.  roots: the
         rows level 1 holds instead of Init (init(roots)).  predicates: a
         set audited on every level right after it is produced, Init's included
         (audit_predicates); the run stops with VIOLATION at the first level that
-        holds a state on which a definition is false.  actions: a step set
-        checked after them on the steps out of every level (audit_steps), before
-        the next step(): every step out of every reachable in-model state is
-        checked, and the run stops at the first level with a false step."""
+        holds a state on which a definition is false.  constraint: a state set
+        that prunes every level, Init's included, after the predicates have
+        seen it whole (constrain; TLC's CONSTRAINT): dropped states are neither
+        counted nor expanded.  actions: a step set checked after them on the
+        steps out of every level's kept rows (audit_steps), before the next
+        step(): every step out of every reachable in-model state is checked,
+        and the run stops at the first level with a false step."""
         def audited() -> int:
             if self.status == OK and self.levels[-1].new > 0:  # (the last, empty level is skipped)
                 if predicates is not None and self.audit_predicates(predicates).status == VIOLATION:
                     self.status = VIOLATION
+                elif constraint is not None and self.constrain(constraint).status == DONE:
+                    pass  # (constrain set the status: nothing is left to expand)
                 elif actions is not None and self.audit_steps(actions).status == VIOLATION:
                     self.status = VIOLATION
             return self.status
@@ -1008,6 +1063,29 @@ class Checker:
         trace() ends in that step: the row, then its successor."""
         return self._audit_set(_lib.rtla_pred_step_frontier, "rtla_pred_step_frontier", actions)
 
+    def constrain(self, preds: Predicates) -> ConstrainResult:
+        """Prune the level last produced by a compiled state set, in place on
+        the GPU (rtla_pred_constrain; TLC's CONSTRAINT):
+        a row is kept iff every definition is TRUE on it; kept rows keep their
+        order.  levels[-1].new and distinct become the post-drop values, and
+        everything that reads the level afterwards -- step, audits, simulate,
+        digests, checkpoint -- sees the kept rows only.  Status DONE: no row is
+        kept and the search is finished.  An evaluation error raises
+        RtlaError(E_SPEC) and leaves the level as it was."""
+        st = _ConstrainStats()
+        self._pred_viol = None
+        rc = _lib.rtla_pred_constrain(self._h, _set_handle(preds, False), C.byref(st))
+        if rc < 0:
+            raise RtlaError(rc, "rtla_pred_constrain", st.flags)
+        if self.levels:
+            self.levels[-1].new = st.kept
+        self.distinct = st.distinct_total
+        if rc == DONE:
+            self.status = DONE
+        return ConstrainResult(status=rc, level=st.level, examined=st.examined, kept=st.kept, dropped=st.dropped,
+                               counts={nm: st.counts[k] for k, nm in enumerate(preds.names)}, start=st.start,
+                               eval_ms=st.eval_ms, move_ms=st.move_ms, distinct_total=st.distinct_total)
+
     def _audit_set(self, fn, what: str, preds: Predicates) -> AuditResult:
         st = _AuditStats()
         self._pred_viol = None
@@ -1031,14 +1109,16 @@ class Checker:
 
 
 def check(cfg: Config, trace: bool = True, predicates: Optional[Predicates] = None,
-          actions: Optional[Predicates] = None, roots=None) -> Result:
+          actions: Optional[Predicates] = None, roots=None, constraint: Optional[Predicates] = None) -> Result:
     """Exhaustive BFS of the model (TLC `-workers N` breadth-first mode), from
     Init or from the rows `roots` (Checker.init).
     predicates: user-defined invariants checked on every level (Checker.run);
     actions: action properties checked on the steps out of every level;
-    Result.violation then names the false definitions."""
+    Result.violation then names the false definitions.  constraint: a state
+    set that prunes every level (TLC's CONSTRAINT; Checker.constrain): the
+    counts, the depth and the levels are those of the constrained search."""
     with Checker(cfg) as ck:
-        st = ck.run(predicates=predicates, actions=actions, roots=roots)
+        st = ck.run(predicates=predicates, actions=actions, roots=roots, constraint=constraint)
         res = Result(distinct=ck.distinct, generated=ck.generated, levels=list(ck.levels))
         res.depth = sum(1 for lv in ck.levels if lv.new > 0)
         res.seconds = sum(lv.seconds for lv in ck.levels)
