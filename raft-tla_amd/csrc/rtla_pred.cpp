@@ -235,31 +235,34 @@ struct Compiler {
   }
 
   // ---- expressions, lowest precedence first
+  // TLA+'s table: `=>` (1-1) binds looser than `<=>` (2-2), and neither has a chain.
   Val expr() {
     Nest g(*this);
-    Val a = imp();
-    while (cur().k == K_IFF) {
-      const Token op = take();
-      want(a, T_BOOL, op);
-      Val b = imp();
-      want(b, T_BOOL, op);
-      emit(P_EQ, 0, 0, -1);
-      a.cost = cadd(cadd(a.cost, b.cost), 1);
-    }
-    return a;
-  }
-  Val imp() {
-    Nest g(*this);
-    Val a = disj();
+    Val a = iff();
     if (cur().k == K_IMP) {
       const Token op = take();
       want(a, T_BOOL, op);
       emit(P_NOT, 0, 0, 0);
       const int j = emit(P_JTK, 0, 0, -1);
-      Val b = imp();
+      Val b = iff();
       want(b, T_BOOL, op);
       patch(j);
       a.cost = cadd(cadd(a.cost, b.cost), 2);
+      if (cur().k == K_IMP) fail(cur(), "'a => b => c' has no parse in TLA+: parenthesise one of the two");
+    }
+    return a;
+  }
+  Val iff() {
+    Nest g(*this);
+    Val a = disj();
+    if (cur().k == K_IFF) {
+      const Token op = take();
+      want(a, T_BOOL, op);
+      Val b = disj();
+      want(b, T_BOOL, op);
+      emit(P_EQ, 0, 0, -1);
+      a.cost = cadd(cadd(a.cost, b.cost), 1);
+      if (cur().k == K_IFF) fail(cur(), "'a <=> b <=> c' has no parse in TLA+: parenthesise one of the two");
     }
     return a;
   }

@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 import limits
+import predgen
 import raft_values as rv
 import rtla
 from test_safety_host import ALL, SHAPES, py_mask
@@ -215,6 +216,10 @@ COMPILE_ERRORS = [
     ("P == TRUE\nP == FALSE", "2:1: 'P' is defined twice"),
     ("P == \\A i \\in Server : i < i", "1:26: type error"),
     ("P == Min(1) = 1", "1:11: expected ,"),
+    # TLA+ has no parse for a chain of => or of <=>
+    ("P == TRUE => FALSE => TRUE", "1:20: 'a => b => c' has no parse in TLA+: parenthesise one of the two"),
+    ("P == TRUE <=> FALSE\n  <=> TRUE", "2:3: 'a <=> b <=> c' has no parse in TLA+: parenthesise one of the two"),
+    ("P == TRUE => FALSE <=> TRUE => FALSE", "1:29: 'a => b => c' has no parse in TLA+"),
 ]
 
 
@@ -288,6 +293,9 @@ def test_threads_empty_batch_and_layout_binding():
 def corpus():
     texts = [MCPRED] + [t for t, _ in COMPILE_ERRORS] + [a for a, _ in UNGUARDED] + [b for _, b in UNGUARDED]
     texts += ["%s == %s" % (n, s) for n, s, _ in FIELD_PREDICATES]
+    generated = [d for d in predgen.standard_corpus() if not d[2]]   # every fourth generated state definition
+    texts += [predgen.definition(*d) for d in generated[::4]]
+    assert len(texts) >= 40 + 45
     return texts
 
 

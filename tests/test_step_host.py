@@ -14,6 +14,7 @@ import pytest
 
 import hostmodel
 import limits
+import predgen
 import raft_values as rv
 import rtla
 import tla_text
@@ -386,6 +387,9 @@ def corpus():
     texts = [MCACTIONS, probe_text(PROBE_SETS[0]), probe_text(PROBE_SETS[1]), "Stutter == [][FALSE]_vars"]
     texts += [t for t, _ in COMPILE_ERRORS]
     texts += ["A == " + _act(x) for pair in UNGUARDED for x in pair]
+    generated = [d for d in predgen.standard_corpus() if d[2]]   # 40 of the 64 generated action definitions
+    texts += [predgen.definition(*d) for k, d in enumerate(generated) if k % 8 < 5]
+    assert len(texts) >= 40 + 24
     return texts
 
 
